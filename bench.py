@@ -15,8 +15,15 @@ independent chunks (replicas, weak scaling), value = all ranks' chunks /
 max-over-ranks time; sequence: the ranks share one sequence through the
 ChunkPipeline baton ring (strong scaling).  Prints ONE JSON line on rank 0 with the roofline of
 the dominant kernel (global attention) measured with HIP events on the
-stream it is launched on, and the CPU baseline (the oracle's fp32 path on a
-bounded sample of the same workload).
+stream it is launched on, inside the timed steps.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.
+--full adds what needs runs of its own after the timed steps: the CPU baseline
+(the oracle's fp32 path on a bounded sample of the same workload), the MFMA
+peak probe, and for the sequence workload the recurrence probe and ring model.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy
+(float32, a fixed seeded sample of the large arrays); the inputs are seeded, so
+two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -221,6 +228,52 @@ class EventTimer:
         return sum(s.elapsed_time(e) for s, e in self.pairs) / len(self.pairs)
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much array data (float32)
+
+
+def _named_arrays(obj, prefix, out):
+    """Flatten what a step returned (tensors nested in dicts / lists / tuples)
+    into (name, tensor) pairs; anything that is not a tensor is left out."""
+    if isinstance(obj, torch.Tensor):
+        out.append((prefix or "output", obj))
+    elif isinstance(obj, dict):
+        for k in obj:
+            _named_arrays(obj[k], f"{prefix}_{k}" if prefix else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_arrays(v, f"{prefix}_{i}" if prefix else str(i), out)
+    return out
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: ``outputs`` (what the last timed step returned) as
+    <path>/<name>.npy, float32.  An array goes out whole while all of them fit
+    DUMP_BUDGET_BYTES; otherwise every array larger than its equal share is
+    cut to a sample of that many elements at flat indices drawn once from
+    numpy's default_rng(0) (sorted, the same for every run and build)."""
+    import numpy as np
+    named = [(n, t.detach()) for n, t in _named_arrays(outputs, "", []) if t.numel() > 0]
+    os.makedirs(path, exist_ok=True)
+    if not named:
+        return []
+    share = DUMP_BUDGET_BYTES // 4 // len(named)
+    if sum(t.numel() for _, t in named) * 4 <= DUMP_BUDGET_BYTES:
+        share = max(t.numel() for _, t in named)
+    written = []
+    for name, t in named:
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        if a.size == t.numel():
+            a = a.reshape(tuple(t.shape))
+        safe = "".join(c if (c.isalnum() or c in "-_.") else "_" for c in name)
+        np.save(os.path.join(path, safe + ".npy"), a)
+        written.append(safe)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -247,7 +300,16 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=min(16, os.cpu_count() or 1))
     ap.add_argument("--cpu-runs", type=int, default=1,
                     help="point workload: timed full-chunk CPU runs after the warm-up (BASELINE.md §3 asks for 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the measurements that need runs of their own: the CPU "
+                         "baseline, the MFMA peak probe, the sequence workload's recurrence probe and ring model "
+                         "(off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of each array where the whole would pass 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is not None:
         args.workload, seq, args.height, args.frames, args.overlap, args.memory_tokens = CONFIGS[args.config]
         if seq is not None:
@@ -269,6 +331,7 @@ def main():
         dist.init_process_group("nccl")
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
+    args.dump = args.dump_outputs is not None and rank == 0
 
     from aligned_vggt import _native
     from aligned_vggt.backbone.aggregator import Aggregator
@@ -281,6 +344,7 @@ def main():
     if args.workload != "aggregator":
         return bench_full(args, world, rank, dev)
 
+    dump = args.dump
     agg = Aggregator().to(dev)
     synthetic_init_(agg, seed=0)
     agg.eval()
@@ -301,9 +365,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     timer.active = True
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if dump and i == args.steps - 1:
+            last = step()  # held only when it is written out: the other steps free theirs as before
+        else:
+            step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -315,6 +383,9 @@ def main():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if dump:
+        dump_outputs(args.dump_outputs, {"tokens_layer%d" % k: o for k, o in zip(keep, last)})
+        del last
 
     fl = agg_flops(S=args.frames)
     chunks = args.steps * world
@@ -351,12 +422,12 @@ def main():
                          "traffic_provenance": _counter_provenance("attn_traffic.json")},
             "mfma_util_pmc_provenance": _counter_provenance("step_mfma.json"),
         }
-        if os.environ.get("VGGT_MFMA_PROBE", "1") != "0":
+        if args.full and os.environ.get("VGGT_MFMA_PROBE", "1") != "0":
             # the peak the roofline is priced against, measured on this device after the timed
             # region: back-to-back 32x32x16 bf16 MFMAs, sustained TF/s + clock
             line["mfma_peak_measured"] = {"random_operands": _native.mfma_probe(random=True),
                                           "zero_operands": _native.mfma_probe(random=False)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args.cpu_threads)
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -438,6 +509,7 @@ def bench_full(args, world, rank, dev):
             for k in ("depth", "depth_conf", "images", "pose_enc", "memory_tokens"):
                 if k in ctx["c"] and isinstance(ctx["c"][k], list) and len(ctx["c"][k]) > 2:
                     del ctx["c"][k][0]
+            return ctx["c"]
         n_chunks_step = world
     else:
         # the sequence resident in HBM before the timed region (the bench contract);
@@ -447,16 +519,20 @@ def bench_full(args, world, rank, dev):
         P1 = 6 + (H // 14) * (W // 14)
 
         def step():
-            pipe.run(seq, S, ov, token_dims=(P1, 1024), memory_shape=(1, nm, 512) if nm > 0 else None)
+            return pipe.run(seq, S, ov, token_dims=(P1, 1024), memory_shape=(1, nm, 512) if nm > 0 else None)
         n_chunks_step = len(generate_chunks(args.seq_frames, "chunk_overlap", S, ov))
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if args.dump and i == args.steps - 1:
+            last = step()
+        else:
+            step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -465,8 +541,11 @@ def bench_full(args, world, rank, dev):
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump:
+        dump_outputs(args.dump_outputs, last)
+        del last
     recurrence = ring_model = None
-    if args.workload == "sequence" and os.environ.get("VGGT_RECURRENCE_PROBE", "1") != "0":
+    if args.full and args.workload == "sequence" and os.environ.get("VGGT_RECURRENCE_PROBE", "1") != "0":
         recurrence = _recurrence_probe(pipe, step, lambda: pipe.prepare(seq, S, ov), n_chunks_step,
                                        dt / args.steps * 1e3, world)
         if world == 1:
@@ -491,7 +570,8 @@ def bench_full(args, world, rank, dev):
             # BASELINE.md §3 row C3 (configs[2]'s sequence through the fp32 oracle at 16 threads: 2,350 s, too
             # long to re-time inside a bench run) as measured on a GPU-box host, labelled as such
             "cpu_baseline": (_measured_row("C3", args.cpu_threads)
-                             if (args.config == 2 and world == 1 and not args.no_cpu_baseline) else None)}),
+                             if (args.full and args.config == 2 and world == 1 and not args.no_cpu_baseline)
+                             else None)}),
               flush=True)
 
 
@@ -663,7 +743,7 @@ def bench_point(args, world, rank, dev):
     synthetic_init_(model, seed=0)
     condition_pose_outputs_(model)
     cpu_sd = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     model = model.to(dev).eval()
     imgs = synthetic_images(1, S, H, W, seed=1234 + rank, device=dev)
@@ -680,9 +760,13 @@ def bench_point(args, world, rank, dev):
         dist.barrier()
     torch.cuda.synchronize()
     timer.active = True
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if args.dump and i == args.steps - 1:
+            last = step()
+        else:
+            step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -697,6 +781,9 @@ def bench_point(args, world, rank, dev):
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump:
+        dump_outputs(args.dump_outputs, last)
+        del last
     fl = agg_flops(S=S, H=H, W=W)
     value = args.steps * world / dt
     attn_tf = fl["global_attn_launch"] / (attn_ms * 1e-3) / 1e12 if attn_ms else None
@@ -846,7 +933,7 @@ def bench_train(args, world, rank, dev):
         fwd_bwd = GraphedStep(fwd_bwd, modules=[head], warmup=2, device=dev)
 
     def step():
-        fwd_bwd()
+        loss = fwd_bwd()
         if world > 1:  # one bucketed all-reduce of every gradient over RCCL (DDP semantics: mean)
             grads = [p.grad for p in head.parameters() if p.grad is not None]
             flat = torch.cat([g.reshape(-1) for g in grads])
@@ -858,15 +945,20 @@ def bench_train(args, world, rank, dev):
                 off += g_.numel()
         torch.nn.utils.clip_grad_norm_(head.parameters(), 1.0)
         opt.step()
+        return loss
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if args.dump and i == args.steps - 1:
+            last = step()
+        else:
+            step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -876,6 +968,8 @@ def bench_train(args, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
         dist.destroy_process_group()
+    if args.dump:  # the step's loss and the parameters it left behind
+        dump_outputs(args.dump_outputs, {"loss": last, "param": dict(head.named_parameters())})
     if rank == 0:
         value = 2 * world * args.steps / dt
         print(json.dumps({
@@ -918,6 +1012,8 @@ def bench_selftest(args, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
         dist.destroy_process_group()
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         n = len(generate_chunks(args.seq_frames, "chunk_overlap", args.frames, args.overlap))
         print(json.dumps({"metric": "selftest chunks/sec (toy model, CPU gloo)", "value": round(n * args.steps / dt, 4),

@@ -13,7 +13,7 @@ for v in ${VARIANTS:-base:}; do
   echo "[$(date +%T)] $name ($envs)"
   env $(echo "$envs" | tr ',' ' ') timeout -k 10 240 python -u scripts/align_prof.py > "$OUT/align_$name.md" 2> "$OUT/align_$name.err" || exit 1
   tail -n 1 "$OUT/align_$name.md"
-  env $(echo "$envs" | tr ',' ' ') VGGT_MFMA_PROBE=0 timeout -k 10 300 python -u bench.py --config "$CFG" --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c${CFG}_$name.out" 2> "$OUT/c${CFG}_$name.err" || exit 1
+  env $(echo "$envs" | tr ',' ' ') VGGT_MFMA_PROBE=0 timeout -k 10 300 python -u bench.py --full --config "$CFG" --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c${CFG}_$name.out" 2> "$OUT/c${CFG}_$name.err" || exit 1
   grep '^{' "$OUT/c${CFG}_$name.out" | tail -1 > "$OUT/c${CFG}_$name.json"
   python3 -c "
 import json,sys; d=json.load(open('$OUT/c${CFG}_$name.json')); r=d['recurrence']; p=d['ring_model']['predicted']['8']

@@ -27,9 +27,9 @@ fi
 if [ "$WHAT" = benches ] || [ "$WHAT" = all ]; then
   step headline 240 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline || exit $?
   step headline_attn16 240 env VGGT_ATTN16=1 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline || exit $?
-  step c3 300 python -u bench.py --config 3 --steps 3 --warmup 2 || exit $?
-  step c3_eager_align 300 env VGGT_ALIGN_GRAPH=0 VGGT_ALIGN_PREFIX=0 python -u bench.py --config 3 --steps 3 --warmup 2 || exit $?
-  step c2 300 python -u bench.py --config 2 --steps 3 --warmup 2 || exit $?
+  step c3 300 python -u bench.py --full --config 3 --steps 3 --warmup 2 || exit $?
+  step c3_eager_align 300 env VGGT_ALIGN_GRAPH=0 VGGT_ALIGN_PREFIX=0 python -u bench.py --full --config 3 --steps 3 --warmup 2 || exit $?
+  step c2 300 python -u bench.py --full --config 2 --steps 3 --warmup 2 || exit $?
   step c0 240 python -u bench.py --config 0 --steps 10 --warmup 3 --no-cpu-baseline || exit $?
   step chunk 240 python -u bench.py --workload chunk --steps 5 --warmup 2 || exit $?
 fi

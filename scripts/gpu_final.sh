@@ -10,9 +10,9 @@ timeout -k 10 720 python -u -m pytest tests -m gpu -x -v -s --timeout 600 --time
 tail -1 "$OUT/pytest.out"
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.out" 2>&1 || { tail "$OUT/smoke.out"; exit 1; }
 tail -1 "$OUT/smoke.out"
-timeout -k 10 300 python -u bench.py > "$OUT/bench.out" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.out" 2> "$OUT/bench.err" || exit 1
 grep '^{' "$OUT/bench.out" | tail -1 | cut -c1-300
-timeout -k 10 400 python -u bench.py --config 3 --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c3.out" 2> "$OUT/c3.err" || exit 1
+timeout -k 10 400 python -u bench.py --full --config 3 --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c3.out" 2> "$OUT/c3.err" || exit 1
 grep '^{' "$OUT/c3.out" | tail -1 | cut -c1-200
-timeout -k 10 300 python -u bench.py --config 0 --steps 10 --warmup 3 > "$OUT/c0.out" 2> "$OUT/c0.err" || exit 1
+timeout -k 10 300 python -u bench.py --full --config 0 --steps 10 --warmup 3 > "$OUT/c0.out" 2> "$OUT/c0.err" || exit 1
 grep '^{' "$OUT/c0.out" | tail -1 | cut -c1-200

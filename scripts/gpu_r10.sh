@@ -23,7 +23,7 @@ for v in ${VARIANTS:-base:}; do
 done
 if [ -n "${C3:-}" ]; then
   echo "[$(date +%T)] c3"
-  env $(echo "$C3" | tr ',' ' ') timeout -k 10 400 python -u bench.py --config 3 --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c3.out" 2> "$OUT/c3.err" || exit 1
+  env $(echo "$C3" | tr ',' ' ') timeout -k 10 400 python -u bench.py --full --config 3 --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/c3.out" 2> "$OUT/c3.err" || exit 1
   grep '^{' "$OUT/c3.out" | tail -1 > "$OUT/c3.json"
 fi
 echo "[$(date +%T)] done"

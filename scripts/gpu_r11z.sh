@@ -28,7 +28,7 @@ if has smoke; then
   step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 fi
 if has head; then
-  step headline 400 python -u bench.py || exit $?
+  step headline 400 python -u bench.py --full || exit $?
   grep '^{' "$OUT/headline.out" | tail -1 > "$OUT/headline.json"
 fi
 if has prof; then
@@ -57,13 +57,13 @@ if has pmc; then
   unset VGGT_MFMA_PROBE
 fi
 if has seq; then
-  step c3 400 python -u bench.py --config 3 --steps 3 --warmup 2 --no-cpu-baseline || exit $?
+  step c3 400 python -u bench.py --full --config 3 --steps 3 --warmup 2 --no-cpu-baseline || exit $?
   grep '^{' "$OUT/c3.out" | tail -1 > "$OUT/c3.json"
-  step c4 400 python -u bench.py --config 4 --steps 3 --warmup 2 --no-cpu-baseline || exit $?
+  step c4 400 python -u bench.py --full --config 4 --steps 3 --warmup 2 --no-cpu-baseline || exit $?
   grep '^{' "$OUT/c4.out" | tail -1 > "$OUT/c4.json"
 fi
 if has c2; then
-  step c2 400 python -u bench.py --config 2 --steps 2 --warmup 1 || exit $?
+  step c2 400 python -u bench.py --full --config 2 --steps 2 --warmup 1 || exit $?
   grep '^{' "$OUT/c2.out" | tail -1 > "$OUT/c2.json"
 fi
 if has chunk; then
@@ -71,7 +71,7 @@ if has chunk; then
   grep '^{' "$OUT/chunk.out" | tail -1 > "$OUT/chunk.json"
 fi
 if has c0; then
-  step c0 300 python -u bench.py --config 0 --steps 10 --warmup 3 || exit $?
+  step c0 300 python -u bench.py --full --config 0 --steps 10 --warmup 3 || exit $?
   grep '^{' "$OUT/c0.out" | tail -1 > "$OUT/c0.json"
 fi
 echo "[$(date +%T)] done"

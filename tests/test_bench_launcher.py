@@ -30,3 +30,37 @@ def test_bench_launches_ranks_itself():
     assert two["value"] > 0 and two["steps"] == 2
     for k, v in one["checksum"].items():
         assert abs(two["checksum"][k] - v) <= 1e-6 * max(1.0, abs(v)), (k, v, two["checksum"][k])
+
+
+def test_dump_outputs_writes_last_step_arrays(tmp_path):
+    """--dump-outputs DIR leaves the last timed step's arrays as DIR/<name>.npy
+    (float32): one file per output the line's checksum names, summing to it;
+    --full is accepted beside it."""
+    import numpy as np
+    a = str(tmp_path / "a")
+    one = _bench("--gpus", "1", "--full", "--dump-outputs", a)
+    assert sorted(os.listdir(a)) == sorted(k + ".npy" for k in one["checksum"])
+    for k, v in one["checksum"].items():
+        x = np.load(os.path.join(a, k + ".npy"))
+        assert x.dtype == np.float32 and x.size > 0
+        assert abs(float(x.astype(np.float64).sum()) - v) <= 1e-5 * max(1.0, abs(v)), (k, v)
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """Past the byte budget every array larger than its share is cut to a fixed
+    seeded sample: same indices on every call, values taken from the array."""
+    import numpy as np
+    import torch
+    import bench  # the repository root is on sys.path (conftest.py)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 100)
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    outs = {"big": big, "pair": [torch.ones(3), torch.zeros(2, 2)], "skipped": None}
+    assert bench.dump_outputs(str(tmp_path), outs) == ["big", "pair_0", "pair_1"]
+    got = np.load(tmp_path / "big.npy")
+    assert got.dtype == np.float32 and got.shape == (33,)
+    assert np.all(np.diff(got) >= 0) and set(got.tolist()) <= set(range(1000))
+    assert np.load(tmp_path / "pair_1.npy").shape == (2, 2)
+    bench.dump_outputs(str(tmp_path / "again"), outs)
+    assert np.array_equal(got, np.load(tmp_path / "again" / "big.npy"))
+    total = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path) if f.endswith(".npy"))
+    assert total <= 4 * 100 + 3 * 128  # the data within the budget, plus one .npy header each
