@@ -75,6 +75,12 @@ const char* vggt_version(void);
 #define VGGT_TUNE_GEMM_BALANCE 10 /* vggt_gemm_bf16 on the persistent form: 1 the whole rounds of row panels
                                      persistent and the remaining rows on the 128x128 form when the last round
                                      would be under 60 % full (bitwise equal), 0 one launch */
+#define VGGT_TUNE_ATTN_TAIL_SPLIT 11 /* vggt_attention_fwd_ws, 8-wave D = 64 default path: 0 the row blocks of the
+                                        launch's last, partial round of workgroups run split over the keys when the
+                                        slot model says it pays (vggt_attention_split_plan), -1 never
+                                        (default; bitwise vggt_attention_fwd), parts | tail_blocks << 8 forced: the last
+                                        tail_blocks (batch, head, row block) units in parts (2..4, clamped to the
+                                        64-key tile count) workgroups each.  Env VGGT_ATTN_TAIL_SPLIT */
 /* (knob 6, the persistent GEMM's DMA-placement bits, is retired: its measured-best placement is the only
    one compiled; vggt_tune(6, ...) returns VGGT_ERR_UNSUPPORTED) */
 int vggt_tune(int knob, int value);
@@ -172,6 +178,23 @@ int vggt_resid_add_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy, 
                              int64_t ldn, void* stream);
 
 /*
+ * The two row passes of a block (after proj, after fc2) with the first one's
+ * store of x deferred into the second; bitwise the results of two
+ * vggt_resid_add_layernorm calls:
+ *   vggt_resid_add_layernorm_nostore: xn[m] = LayerNorm(x[m] + gamma * y[m]);
+ *     x is read only (xn required).
+ *   vggt_resid_add2_layernorm: x[m] = (x[m] + gamma * y[m]) + gamma2 * y2[m]
+ *     with the same y and gamma again, then out2 / xn as vggt_resid_add_layernorm.
+ * y must stay unchanged between the two calls.
+ */
+int vggt_resid_add_layernorm_nostore(const float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma,
+                                     const float* w, const float* b, float eps, int M, int C, void* xn, int64_t ldn,
+                                     void* stream);
+int vggt_resid_add2_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma, const void* y2,
+                              int64_t ldy2, const float* gamma2, float* out2, int64_t ldo2, const float* w,
+                              const float* b, float eps, int M, int C, void* xn, int64_t ldn, void* stream);
+
+/*
  * In-place per-head LayerNorm (QK-norm) + RoPE on a bf16 [M, ld] buffer:
  * for each row m and head h, the D values at columns col_off + h*D are
  * normalised with (w,b,eps) (skipped if w == NULL) and rotated (rope_mode).
@@ -220,6 +243,30 @@ int vggt_headnorm_rope_out(const void* src, int64_t lds, void* dst, int64_t ldd,
 int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk, int64_t k_bstride,
                        const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo, int64_t o_bstride,
                        int batch, int heads, int nq, int nk, int D, float scale, void* stream);
+
+/*
+ * vggt_attention_fwd with a workspace, the one entry that may split keys: on
+ * the 8-wave D = 64 default path (nq >= 4096) the (batch, head, 256-row block)
+ * units of the launch's last, partial round of workgroups run as 2..4
+ * workgroups each, one per contiguous range of 64-key tiles, dispatched behind
+ * the whole units in the same launch; each leaves its row offsets, row sums
+ * and unnormalised fp32 accumulator (m, l, O) in ws, and a second small launch
+ * on the same stream merges them in a fixed order (run-to-run bitwise stable;
+ * no atomics, no flags) and writes those rows of o.  All other rows are
+ * bitwise those of vggt_attention_fwd.  ws: 16-byte aligned, at least
+ * vggt_attention_ws_bytes(...) bytes for the same shape, stream and
+ * VGGT_TUNE_ATTN_TAIL_SPLIT value (0 bytes: the launch will not split); one
+ * buffer may serve every launch of a stream.  ws == NULL never splits.
+ * vggt_attention_split_plan is the policy alone (host arithmetic, no device
+ * call): 1 and the tail size / parts for a launch on `cus` compute units
+ * (two 8-wave workgroups per CU), else 0.
+ */
+int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                          int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
+                          int64_t o_bstride, int batch, int heads, int nq, int nk, int D, float scale, void* ws,
+                          size_t ws_bytes, void* stream);
+size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream);
+int vggt_attention_split_plan(int batch, int heads, int nq, int nk, int D, int cus, int* tail_blocks, int* parts);
 
 /*
  * DINOv2 patch-embed input: ResNet-normalise fp32 images (F,3,H,W) and write

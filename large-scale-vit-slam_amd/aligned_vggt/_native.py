@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from .runtime import scratch_table
+from .runtime import Workspace, scratch_table
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("VGGT_MI355X_LIB", os.path.join(_PKG_ROOT, "lib", "libvggt_mi355x.so"))
@@ -45,9 +45,15 @@ _SIGS = {
     "vggt_gated_update_tail": [_vp, _vp, _vp, _i, _i, _vp, _vp],
     "vggt_layernorm": [_vp, _i, _i64, _vp, _vp, _f, _i, _i, _vp, _i, _i64, _vp],
     "vggt_resid_add_layernorm": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f, _i, _i, _vp, _i64, _vp],
+    "vggt_resid_add_layernorm_nostore": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _f, _i, _i, _vp, _i64, _vp],
+    "vggt_resid_add2_layernorm": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f, _i, _i, _vp,
+                                  _i64, _vp],
     "vggt_headnorm_rope": [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _vp, _vp, _i, _vp],
     "vggt_attention_fwd": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i, _f,
                            _vp],
+    "vggt_attention_fwd_ws": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i,
+                              _f, _vp, ctypes.c_size_t, _vp],
+    "vggt_attention_split_plan": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_patch_im2col": [_vp, _i, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _i, _vp],
     "vggt_dino_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "vggt_special_tokens": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp],
@@ -108,7 +114,7 @@ _SIGS = {
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
-           "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i]}
+           "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp]}
 
 _lib = None
 
@@ -154,6 +160,7 @@ TUNE_LINEAR_ONE_LAUNCH = 6
 TUNE_LINEAR_SPLIT_K = 7
 TUNE_LINEAR_WK = 8
 TUNE_GEMM_BALANCE = 10
+TUNE_ATTN_TAIL_SPLIT = 11  # 0 plan, -1 off, parts | tail_blocks << 8 forced (include/vggt_mi355x.h)
 
 
 def tune(knob: int, value: int) -> int:
@@ -329,6 +336,36 @@ def resid_add_layernorm(x: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, o
     _check(rc, "vggt_resid_add_layernorm")
 
 
+def resid_add_layernorm_nostore(x: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, w: Optional[torch.Tensor],
+                                b: Optional[torch.Tensor], eps: float, xn: torch.Tensor) -> None:
+    """xn = LayerNorm(x + gamma * y) with x left as it is: the first of the two
+    deferred row passes of a block (resid_add2_layernorm stores x)."""
+    _dev(x, "resid_add_layernorm_nostore")
+    M, C = x.shape
+    assert x.dtype == torch.float32 and y.dtype == torch.bfloat16 and y.shape[0] == M and y.shape[1] == C
+    assert xn.dtype == torch.bfloat16 and xn.shape[0] == M and xn.shape[1] == C
+    rc = lib().vggt_resid_add_layernorm_nostore(_p(x), _ld(x), _p(y), _ld(y), _p(gamma), _p(w), _p(b), float(eps), M,
+                                                C, _p(xn), _ld(xn), _stream())
+    _check(rc, "vggt_resid_add_layernorm_nostore")
+
+
+def resid_add2_layernorm(x: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, y2: torch.Tensor,
+                         gamma2: torch.Tensor, out2: Optional[torch.Tensor], w: Optional[torch.Tensor],
+                         b: Optional[torch.Tensor], eps: float, xn: Optional[torch.Tensor]) -> None:
+    """x = (x + gamma * y) + gamma2 * y2, then out2 / xn as resid_add_layernorm:
+    bitwise resid_add_layernorm(x, y, gamma) followed by resid_add_layernorm(x, y2, gamma2, ...)."""
+    _dev(x, "resid_add2_layernorm")
+    M, C = x.shape
+    assert x.dtype == torch.float32
+    for t in (y, y2):
+        assert t.dtype == torch.bfloat16 and t.shape[0] == M and t.shape[1] == C
+    assert xn is None or (xn.dtype == torch.bfloat16 and xn.shape[0] == M and xn.shape[1] == C)
+    rc = lib().vggt_resid_add2_layernorm(_p(x), _ld(x), _p(y), _ld(y), _p(gamma), _p(y2), _ld(y2), _p(gamma2),
+                                         _p(out2), _ld(out2) if out2 is not None else 0, _p(w), _p(b), float(eps), M,
+                                         C, _p(xn), _ld(xn) if xn is not None else 0, _stream())
+    _check(rc, "vggt_resid_add2_layernorm")
+
+
 def headnorm_rope(buf: torch.Tensor, col_off: int, H: int, D: int, w: Optional[torch.Tensor],
                   b: Optional[torch.Tensor], eps: float, mode: int = ROPE_NONE, pos: Optional[torch.Tensor] = None,
                   period: int = 1, cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None) -> None:
@@ -380,13 +417,30 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor
     _dev(q, "attention")
     sc = D ** -0.5 if scale is None else scale
     L = lib()
+    # key-split tail of a long launch (vggt_attention_fwd_ws): the partials live in one
+    # named workspace buffer, reused by every layer of the stream
+    ws, nbytes = None, 0
+    if D == 64 and nq >= 4096:
+        nbytes = L.vggt_attention_ws_bytes(batch, heads, nq, nk, D, _stream())
+        if nbytes:
+            ws = Workspace.get(q.device).buf("attn_tail_parts", 1, (nbytes + 3) // 4)
 
     def call():
-        return L.vggt_attention_fwd(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), k_bstride, _p(o),
-                                    _ld(o), o_bstride, batch, heads, nq, nk, D, float(sc), _stream())
+        return L.vggt_attention_fwd_ws(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), k_bstride,
+                                       _p(o), _ld(o), o_bstride, batch, heads, nq, nk, D, float(sc), _p(ws), nbytes,
+                                       _stream())
 
     rc = EVENT_HOOK(tag, call) if (EVENT_HOOK is not None and tag is not None) else call()
-    _check(rc, "vggt_attention_fwd")
+    _check(rc, "vggt_attention_fwd_ws")
+
+
+def attention_split_plan(batch: int, heads: int, nq: int, nk: int, D: int, cus: int):
+    """vggt_attention_split_plan (host arithmetic only): (tail_blocks, parts) when a
+    launch of this shape on ``cus`` compute units should split its tail, else None."""
+    t, p = ctypes.c_int(0), ctypes.c_int(0)
+    if not lib().vggt_attention_split_plan(batch, heads, nq, nk, D, cus, ctypes.byref(t), ctypes.byref(p)):
+        return None
+    return t.value, p.value
 
 
 def attention_stamps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, batch: int, heads: int,

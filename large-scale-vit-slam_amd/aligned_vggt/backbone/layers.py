@@ -84,7 +84,14 @@ _FUSED_QKV128 = os.environ.get("VGGT_FUSED_QKV128", "1") != "0"
 # 154x518 sequence chunk (6,592 rows, fc2 = 140 tiles, less than one round) the
 # sequence measured 1651 vs 1661 ms per 43 chunks (neutral to slightly worse),
 # the 518^2 chunk 138.9 -> 137.8 ms and configs[2] 695 -> 689 ms (profiles/r4).
-_FUSED_ADD_LN = int(os.environ.get("VGGT_FUSED_ADD_LN", "3"))
+# Bit 4 (only with bits 1 and 2): the proj pass does not store x -- it keeps
+# x' = x + ls1 * proj in registers for norm2 -- and the fc2 pass forms
+# (x + ls1 * proj) + ls2 * fc2 from x, blk_pj and the fc2 output with the same
+# fp32 expression (vggt_resid_add_layernorm_nostore / vggt_resid_add2_layernorm):
+# 495 instead of 540 MB per block over the two passes, bitwise equal results;
+# aggregator step 91.08-91.55 -> 90.44-90.46 ms (3 x 2 same-box alternation,
+# profiles/r12/ab_attn_tail_split.md).
+_FUSED_ADD_LN = int(os.environ.get("VGGT_FUSED_ADD_LN", "7"))
 _FUSED_ADD_LN_MIN_ROWS = 16384
 
 
@@ -186,12 +193,19 @@ class Block(nn.Module):
         w, b = pack_linear(self.attn.proj)
         fal = _FUSED_ADD_LN if M >= _FUSED_ADD_LN_MIN_ROWS else 0
         yield_point(fine=True)
+        # bit 4: the residual store of the proj pass deferred into the fc2 pass (blk_pj stays live until then)
+        defer = (fal & 7) == 7 and C in (256, 512, 1024, 2048) and isinstance(self.norm2, nn.LayerNorm)
+        pj = None
         if (fal & 2) and C in (256, 512, 1024, 2048) and isinstance(self.norm2, nn.LayerNorm):
             # proj with a plain bf16 epilogue, then one row pass: x += ls1 * proj, xn = norm2(x)
             pj = ws.buf("blk_pj", M, C, torch.bfloat16)
             N.gemm_bf16(ao, w, b, pj, N.EPI_BF16)
-            N.resid_add_layernorm(xs, pj, self._gamma(self.ls1, C, x.device), None, self.norm2.weight,
-                                  self.norm2.bias, self.norm2.eps, xn)
+            if defer:
+                N.resid_add_layernorm_nostore(xs, pj, self._gamma(self.ls1, C, x.device), self.norm2.weight,
+                                              self.norm2.bias, self.norm2.eps, xn)
+            else:
+                N.resid_add_layernorm(xs, pj, self._gamma(self.ls1, C, x.device), None, self.norm2.weight,
+                                      self.norm2.bias, self.norm2.eps, xn)
         else:
             N.gemm_bf16(ao, w, b, xs, N.EPI_RESID_F32, gamma=self._gamma(self.ls1, C, x.device))
             N.layernorm(xs, self.norm2.weight, self.norm2.bias, self.norm2.eps, xn)
@@ -210,6 +224,11 @@ class Block(nn.Module):
         # arithmetic as the EPI_RESID_F32 epilogue).
         N.gemm_bf16(hid, w, b, ao, N.EPI_BF16)
         ln = next_norm if isinstance(next_norm, nn.LayerNorm) else None
+        if defer:
+            N.resid_add2_layernorm(xs, pj, self._gamma(self.ls1, C, x.device), ao, self._gamma(self.ls2, C, x.device),
+                                   out2, ln.weight if ln is not None else None, ln.bias if ln is not None else None,
+                                   ln.eps if ln is not None else 0.0, xn if ln is not None else None)
+            return ln is not None
         N.resid_add_layernorm(xs, ao, self._gamma(self.ls2, C, x.device), out2,
                               ln.weight if ln is not None else None, ln.bias if ln is not None else None,
                               ln.eps if ln is not None else 0.0, xn if ln is not None else None)

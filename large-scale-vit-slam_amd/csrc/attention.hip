@@ -27,8 +27,12 @@
 //    share an XCD so its K/V stream is served from one L2.
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "tune.h"
@@ -52,7 +56,18 @@ struct AttnArgs {
   int batch, heads, nq, nk;
   float c;     // scale * log2(e)
   float* lse;  // optional [batch*heads*nq]: log2 sum exp2(scores * c) per row (training recompute)
+  // key-split tail (VAR & 8192 only): workgroups [0, n_full) are whole units (b, h, row block) in
+  // linear order; the units from n_full on run as `parts` workgroups each, part p over the keys
+  // [p * part_tiles * 64, ...) (the last part takes the rest), and leave (m, l, O) in ws
+  int n_full, parts, part_tiles;
+  float* ws;
 };
+
+// Partial of one (tail unit, part): the fp32 O accumulators in register order
+// [wave][db * 4 + gq][lane] float4 (every store instruction writes 1 KiB
+// contiguous), then per row (m, l) as float2.
+constexpr int SPLIT_BQ = 256;
+constexpr int SPLIT_SLAB = SPLIT_BQ * 64 + 2 * SPLIT_BQ;  // floats
 
 // LDS-DMA: 16 B per lane from buffer `rsrc` at per-lane byte offset `voff`
 // into the wave-uniform LDS address `lds` (+lane*16).  Inline asm keeps the
@@ -122,15 +137,34 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
   }
   const int nqb = (a.nq + BQ - 1) / BQ;
-  const int bid = xcd_remap(blockIdx.x, nqb * a.heads * a.batch);
+  // VAR & 8192 (key-split tail): the first n_full workgroups are whole units,
+  // the others one part of a tail unit each -- its keys [key0, key0 + nk); the
+  // XCD remap runs within either range (dispatch follows the block index, so
+  // the whole units keep the low indices)
+  constexpr bool SPLIT = (VAR & 8192) != 0;
+  int bid, nk = a.nk, key0 = 0, slab = -1;
+  if constexpr (SPLIT) {
+    const int bx = blockIdx.x;
+    if (bx < a.n_full) {
+      bid = xcd_remap(bx, a.n_full);
+    } else {
+      slab = xcd_remap(bx - a.n_full, (int)gridDim.x - a.n_full);
+      const int part = slab % a.parts;
+      bid = a.n_full + slab / a.parts;
+      key0 = part * a.part_tiles * BKV;
+      nk = part == a.parts - 1 ? a.nk - key0 : a.part_tiles * BKV;
+    }
+  } else {
+    bid = xcd_remap(blockIdx.x, nqb * a.heads * a.batch);
+  }
   const int qb = bid % nqb;
   const int bh = bid / nqb;
   const int h = bh % a.heads;
   const int b = bh / a.heads;
 
   const bf16_t* qp = a.q + (int64_t)b * a.qbs * a.ldq + h * D;
-  const bf16_t* kp = a.k + (int64_t)b * a.kbs * a.ldk + h * D;
-  const bf16_t* vp = a.v + (int64_t)b * a.vbs * a.ldv + h * D;
+  const bf16_t* kp = a.k + ((int64_t)b * a.kbs + key0) * a.ldk + h * D;
+  const bf16_t* vp = a.v + ((int64_t)b * a.vbs + key0) * a.ldv + h * D;
 
   // ---- Q fragments = B operand of S^T = K Q^T: Q[q][16ks + 8*hl + j]
   const int qrow = qb * BQ + wave * 32 + (lane & 31);
@@ -170,7 +204,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   // 32-bit scalar descriptor arithmetic (host: nk * ld * 2 < 2^31): a 64-bit
   // "remaining bytes" compare has no SALU form and would run on the VALU
   const int kstep = BKV * (int)a.ldk * 2, vstep = BKV * (int)a.ldv * 2;
-  const int kbytes = a.nk * (int)a.ldk * 2, vbytes = a.nk * (int)a.ldv * 2;
+  const int kbytes = nk * (int)a.ldk * 2, vbytes = nk * (int)a.ldv * 2;
 
   auto stage = [&](int buf, int t) {
     const int ko = kstep * t, vo = vstep * t;
@@ -219,7 +253,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   float lim = THR, limv = 256.0f;
   bool zero_off = false;
   const float c = a.c;
-  const int nt = (a.nk + BKV - 1) / BKV;
+  const int nt = (nk + BKV - 1) / BKV;
   // VAR & 1024: per-wave cycle sums of the tile segments (s_memtime, one scalar
   // statement with its lgkmcnt(0)); 32-bit sums, no tile counter (the host
   // knows the tile count): so instrumented, the kernel keeps the default's 113
@@ -302,13 +336,13 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     f32x16 s[2] = {sc.v[0], sc.v[1]};
     const int kv0 = t * BKV;
     auto mask = [&]() {
-      if (kv0 + BKV > a.nk) {
+      if (kv0 + BKV > nk) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-            if (key >= a.nk) s[kb][r] = -INFINITY;
+            if (key >= nk) s[kb][r] = -INFINITY;
           }
       }
     };
@@ -660,7 +694,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       for (int t = t0; t < nt; t += 2) {
         VGGT_SEG(-1);
         if (t + 1 < nt) stage(1, t + 1);
-        if ((VAR & 256) && (t + 1) * BKV <= a.nk) tile_split(I0{}, zc);
+        if ((VAR & 256) && (t + 1) * BKV <= nk) tile_split(I0{}, zc);
         else soft_pv(I0{}, t, qk(I0{}), zc);
         VGGT_SEG(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -669,7 +703,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         VGGT_SEG(4);
         if (t + 1 >= nt) break;
         if (t + 2 < nt) stage(0, t + 2);
-        if ((VAR & 256) && (t + 2) * BKV <= a.nk) tile_split(I1{}, zc);
+        if ((VAR & 256) && (t + 2) * BKV <= nk) tile_split(I1{}, zc);
         else soft_pv(I1{}, t + 1, qk(I1{}), zc);
         VGGT_SEG(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -696,6 +730,20 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   } else {
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
     l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+  }
+  if constexpr (SPLIT) {
+    // a part does not normalise: (m, l, O) to the workspace, merged by attn_split_merge_kernel
+    if (slab >= 0) {
+      float* sp = a.ws + (int64_t)slab * SPLIT_SLAB;
+#pragma unroll
+      for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+          *(f32x4*)(sp + ((wave * (NDB * 4) + db * 4 + gq) * 64 + lane) * 4) =
+              f32x4{o[db][4 * gq], o[db][4 * gq + 1], o[db][4 * gq + 2], o[db][4 * gq + 3]};
+      if (hl == 0) *(f32x2*)(sp + BQ * D + (wave * 32 + lane) * 2) = f32x2{m_run, l_run};
+      return;
+    }
   }
   const float inv = 1.f / l_run;
   if constexpr (VAR & 1024) {
@@ -1001,12 +1049,252 @@ __global__ __launch_bounds__(NW * 64, 16 / NW) void attn16_fwd_kernel(AttnArgs a
   }
 }
 
+// ---------------------------------------------------------------------------
+// Merge of the key-split tail (attn_fwd_kernel, VAR & 8192): for every row of
+// the tail units, over its parts in index order (a fixed order: bitwise stable
+// from run to run), M = max m_i, o = sum 2^(m_i - M) O_i / sum 2^(m_i - M) l_i,
+// rounded to bf16 into the caller's o.  One thread per float4 of a partial, in
+// the partial's own (register) order, so the loads are contiguous per wave and
+// the stores are those of the unsplit epilogue.  Plain loads and stores only.
+__global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a, int n_tail) {
+  constexpr int D = 64;
+  const int tid = blockIdx.x * 256 + threadIdx.x;
+  const int lane = tid & 63, c = (tid >> 6) & 7, wave = (tid >> 9) & 7, tu = tid >> 12;
+  if (tu >= n_tail) return;
+  const int nqb = (a.nq + SPLIT_BQ - 1) / SPLIT_BQ;
+  const int bid = a.n_full + tu;
+  const int qb = bid % nqb, bh = bid / nqb;
+  const int h = bh % a.heads, b = bh / a.heads;
+  const int r = wave * 32 + (lane & 31), hl = lane >> 5;
+  const int qrow = qb * SPLIT_BQ + r;
+  if (qrow >= a.nq) return;
+  const float* sp = a.ws + (int64_t)tu * a.parts * SPLIT_SLAB;
+  float mx = -INFINITY;
+  for (int p = 0; p < a.parts; ++p) mx = fmaxf(mx, sp[(int64_t)p * SPLIT_SLAB + SPLIT_BQ * D + r * 2]);
+  f32x4 num = f32x4{0.f, 0.f, 0.f, 0.f};
+  float den = 0.f;
+  for (int p = 0; p < a.parts; ++p) {
+    const float* pp = sp + (int64_t)p * SPLIT_SLAB;
+    const f32x2 ml = *(const f32x2*)(pp + SPLIT_BQ * D + r * 2);
+    const float w = __builtin_amdgcn_exp2f(ml[0] - mx);
+    num += w * *(const f32x4*)(pp + ((wave * 8 + c) * 64 + lane) * 4);
+    den += w * ml[1];
+  }
+  const float inv = 1.f / den;
+  uint2 pk;
+  pk.x = pack_bf2(num[0] * inv, num[1] * inv);
+  pk.y = pack_bf2(num[2] * inv, num[3] * inv);
+  bf16_t* op = a.o + ((int64_t)b * a.obs + qrow) * a.ldo + h * D;
+  *(uint2*)(op + (c >> 2) * 32 + 8 * (c & 3) + 4 * hl) = pk;
+}
+
+inline int attn_cu_count(hipStream_t s) {
+  static int dev_cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  const int n = vggt_stream_cu_count(s);
+  return n > 0 ? n : dev_cus;
+}
+
+// ---- key-split plan: the slot model (host only, no device call) -----------
+// A CU holds two 8-wave workgroups; the matrix pipe is what they share, so a
+// workgroup alone on its CU runs twice as fast: a CU is one server of rate 2
+// (tiles per tile time) shared by its residents.  Workgroups are dispatched in
+// index order to the CU with the fewest residents as slots free up.  Lengths
+// in 64-key tiles, plus PLAN_UNIT_OVH tiles per workgroup for what does not
+// overlap (Q fragments, the first tile's DMA, the epilogue).
+constexpr double PLAN_UNIT_OVH = 2.0;
+// one tile time of a paired workgroup: 1.284 ms / (2 rounds x 344 tiles) at
+// nq = nk = 16,384 (profiles/r10/attn_quant_r10l.txt); the partials move at
+// about 3.5 TB/s (written once, read once), the merge launch costs ~5 us
+constexpr double PLAN_TILE_US = 1.87, PLAN_BYTES_PER_US = 3.5e6, PLAN_MERGE_US = 5.0;
+// Split only for a modelled gain of at least this fraction of the launch.  The
+// model over-predicts: at 21,984 x 16 heads on 256 CUs it gives 6.5 / 4.8 / 2.7 %
+// for 2 / 4 / 3 parts, measured 2.9 / 2.4 / 1.1 % (1.701 -> 1.651 / 1.656-1.667 /
+// 1.680 ms, spread within an arm 0.3 %: profiles/r12/ab_attn_tail_split.md), so
+// 3 % modelled is about 1.3 % measured, four times that spread.
+constexpr double PLAN_MIN_GAIN = 0.03;
+// ... and only with parts no shorter than the shortest measured to pay (4 parts of
+// 21,984 keys): a part's fixed cost (Q fragments, first tile, partial store, its
+// share of the merge) is unmeasured against fewer tiles
+constexpr int PLAN_MIN_PART_TILES = 86;
+
+struct PlanSeg {
+  int count;
+  double len;
+};
+double plan_makespan(int cus, const PlanSeg* segs, int nseg) {
+  std::vector<double> rem((size_t)cus * 2, 0.0);
+  std::vector<int> cnt((size_t)cus, 0);
+  int seg = 0, left = nseg > 0 ? segs[0].count : 0, resident = 0;
+  double now = 0.0;
+  auto more = [&]() {
+    while (seg < nseg && left == 0) {
+      ++seg;
+      if (seg < nseg) left = segs[seg].count;
+    }
+    return seg < nseg;
+  };
+  for (;;) {
+    // dispatch: every free slot takes the next workgroup, emptiest CUs first
+    for (int want = 0; want < 2; ++want)
+      for (int cu = 0; cu < cus; ++cu)
+        if (cnt[cu] == want && more()) {
+          rem[cu * 2 + cnt[cu]] = segs[seg].len;
+          ++cnt[cu];
+          --left;
+          ++resident;
+        }
+    if (resident == 0) return now;
+    double dt = 1e300;
+    for (int cu = 0; cu < cus; ++cu)
+      for (int i = 0; i < cnt[cu]; ++i) dt = std::min(dt, rem[cu * 2 + i] * cnt[cu] * 0.5);
+    now += dt;
+    for (int cu = 0; cu < cus; ++cu) {
+      const int n = cnt[cu];
+      const double done = dt * 2.0 / (n > 0 ? n : 1);
+      int keep = 0;
+      for (int i = 0; i < n; ++i) {
+        const double r = rem[cu * 2 + i] - done;
+        if (r > 1e-9) rem[cu * 2 + keep++] = r;
+        else --resident;
+      }
+      cnt[cu] = keep;
+    }
+  }
+}
+
+// parts as run: whole tiles per part, the last part takes the rest and is not empty
+inline void split_shape(int nt, int want, int* parts, int* part_tiles) {
+  const int p = std::max(1, std::min(want, nt));
+  *part_tiles = (nt + p - 1) / p;
+  *parts = (nt + *part_tiles - 1) / *part_tiles;
+}
+
 }  // namespace
+
+// Host policy of the key-split tail (see vggt_attention_fwd_ws): 1 and
+// (*tail_blocks, *parts) when a launch of this shape on `cus` CUs should run
+// the row blocks of its last, partial round of workgroups split over the keys,
+// else 0.  Pure host arithmetic: no device is touched.
+extern "C" int vggt_attention_split_plan(int batch, int heads, int nq, int nk, int D, int cus, int* tail_blocks,
+                                         int* parts) {
+  if (tail_blocks) *tail_blocks = 0;
+  if (parts) *parts = 0;
+  if (batch <= 0 || heads <= 0 || nq < 4096 || nk <= 0 || D != 64 || cus <= 0) return 0;
+  const int64_t units64 = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads * batch;
+  const int slots = 2 * cus, nt = (nk + BKV - 1) / BKV;
+  if (units64 < slots || units64 > (1 << 24) || units64 % slots == 0 || nt < 2) return 0;
+  const int units = (int)units64, tail = units % slots;
+  struct Entry {
+    int key[4], tail, parts;
+  };
+  static std::mutex mu;
+  static std::vector<Entry> cache;
+  const int key[4] = {units, nq, nk, cus};
+  std::lock_guard<std::mutex> lk(mu);
+  const Entry* hit = nullptr;
+  for (const Entry& e : cache)
+    if (!memcmp(e.key, key, sizeof key)) hit = &e;
+  if (!hit) {
+    const PlanSeg whole[1] = {{units, nt + PLAN_UNIT_OVH}};
+    const double t0 = plan_makespan(cus, whole, 1);
+    double best = t0;
+    int best_p = 0;
+    for (int want = 2; want <= 4; ++want) {
+      int p, pt;
+      split_shape(nt, want, &p, &pt);
+      if (p != want || pt < PLAN_MIN_PART_TILES) continue;
+      const PlanSeg segs[3] = {{units - tail, nt + PLAN_UNIT_OVH},
+                               {tail * (p - 1), pt + PLAN_UNIT_OVH},
+                               {tail, nt - (p - 1) * pt + PLAN_UNIT_OVH}};
+      // the dispatch order interleaves the parts of a unit; the p - 1 equal parts first is
+      // the same multiset of lengths, and the last part differs by less than a tile per part
+      const double bytes = 2.0 * tail * p * SPLIT_SLAB * 4.0;
+      const double t = plan_makespan(cus, segs, 3) + (bytes / PLAN_BYTES_PER_US + PLAN_MERGE_US) / PLAN_TILE_US;
+      if (t < best) best = t, best_p = want;
+    }
+    if (cache.size() >= 64) cache.clear();
+    cache.push_back(Entry{{units, nq, nk, cus}, tail, (t0 - best) >= PLAN_MIN_GAIN * t0 ? best_p : 0});
+    hit = &cache.back();
+  }
+  if (hit->parts < 2) return 0;
+  if (tail_blocks) *tail_blocks = hit->tail;
+  if (parts) *parts = hit->parts;
+  return 1;
+}
+
+namespace {
+// what the VGGT_TUNE_ATTN_TAIL_SPLIT knob and the plan make of a launch that takes the
+// 8-wave D = 64 default path: tail units and parts as run (0 parts: unsplit)
+void tail_split_of(int batch, int heads, int nq, int nk, int cus, int* tail, int* parts, int* part_tiles) {
+  *tail = *parts = *part_tiles = 0;
+  const int knob = g_vggt_attn_tail_split;
+  const int64_t units = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads * batch;
+  const int nt = (nk + BKV - 1) / BKV;
+  int t = 0, p = 0;
+  if (knob < 0 || units > (1 << 18)) return;  // (the merge kernel indexes 4096 threads per tail unit in 32 bits)
+  if (knob > 0) {
+    p = knob & 0xff;
+    t = (int)std::min<int64_t>(knob >> 8, units);
+  } else if (!vggt_attention_split_plan(batch, heads, nq, nk, 64, cus, &t, &p)) {
+    return;
+  }
+  int pr, pt;
+  split_shape(nt, std::min(p, 4), &pr, &pt);
+  if (pr < 2 || t <= 0) return;
+  *tail = t;
+  *parts = pr;
+  *part_tiles = pt;
+}
+
+bool attn_split_path(int nq, int D) {
+  static const bool dma_half = getenv("VGGT_ATTN_DMA_HALF") ? atoi(getenv("VGGT_ATTN_DMA_HALF")) != 0 : true;
+  return dma_half && g_vggt_attn_variant == 33 && D == 64 && g_vggt_attn_waves == 8 && nq >= 4096;
+}
+}  // namespace
+
+extern "C" size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream) {
+  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !attn_split_path(nq, D)) return 0;
+  int tail, parts, pt;
+  tail_split_of(batch, heads, nq, nk, attn_cu_count((hipStream_t)stream), &tail, &parts, &pt);
+  return (size_t)tail * parts * SPLIT_SLAB * sizeof(float);
+}
+
+static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                              int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
+                              int64_t o_bstride, int batch, int heads, int nq, int nk, int D, float scale, void* ws,
+                              size_t ws_bytes, void* stream);
 
 extern "C" int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                                   int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
                                   int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
                                   float scale, void* stream) {
+  return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
+                            nq, nk, D, scale, nullptr, 0, stream);
+}
+
+// vggt_attention_fwd with a workspace: the only entry that may run the last,
+// partial round of workgroups of the 8-wave D = 64 default path split over the
+// keys (vggt_attention_ws_bytes says how much it needs for this shape under
+// the current VGGT_TUNE_ATTN_TAIL_SPLIT; with ws == NULL it never splits).
+extern "C" int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                                     int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
+                                     int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
+                                     float scale, void* ws, size_t ws_bytes, void* stream) {
+  if (ws && (uintptr_t)ws % 16) return VGGT_ERR_ALIGN;
+  return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
+                            nq, nk, D, scale, ws, ws_bytes, stream);
+}
+
+static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                              int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
+                              int64_t o_bstride, int batch, int heads, int nq, int nk, int D, float scale, void* ws,
+                              size_t ws_bytes, void* stream) {
   if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0) return VGGT_ERR_SHAPE;
   if (D != 64 && D != 128) return VGGT_ERR_UNSUPPORTED;
   if ((ldq | ldk | ldv | ldo) % 8 || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16)
@@ -1056,6 +1344,22 @@ extern "C" int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride,
   // (profiles/r11/ab_attn_dma_half.md).  VGGT_ATTN_DMA_HALF=0: every wave issues its piece.
   static const bool dma_half = getenv("VGGT_ATTN_DMA_HALF") ? atoi(getenv("VGGT_ATTN_DMA_HALF")) != 0 : true;
   if (dma_half && g_vggt_attn_variant == 33 && D == 64 && nw == 8 && !a.lse) {
+    int tail = 0, parts = 0, pt = 0;
+    if (ws) tail_split_of(batch, heads, nq, nk, attn_cu_count(s), &tail, &parts, &pt);
+    if (parts >= 2) {
+      // key-split tail: the last `tail` units as `parts` workgroups each behind the whole
+      // units, in the same launch; then the merge of their partials, on the same stream
+      if (ws_bytes < (size_t)tail * parts * SPLIT_SLAB * sizeof(float)) return VGGT_ERR_SHAPE;
+      a.n_full = nwg - tail;
+      a.parts = parts;
+      a.part_tiles = pt;
+      a.ws = (float*)ws;
+      attn_fwd_kernel<64, 8, 2081 | 8192><<<a.n_full + tail * parts, 512, 0, s>>>(a);
+      HIP_LAUNCH_CHECK();
+      attn_split_merge_kernel<<<tail * 16, 256, 0, s>>>(a, tail);
+      HIP_LAUNCH_CHECK();
+      return VGGT_OK;
+    }
     attn_fwd_kernel<64, 8, 2081><<<nwg, 512, 0, s>>>(a);
     HIP_LAUNCH_CHECK();
     return VGGT_OK;

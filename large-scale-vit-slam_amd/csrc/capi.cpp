@@ -29,6 +29,12 @@ int g_vggt_linear_split_k = env_or("VGGT_LINEAR_SPLIT_K", 128);
 int g_vggt_linear_wk = env_or("VGGT_LINEAR_WK", 64);
 int g_vggt_gemm_balance = env_or("VGGT_GEMM_BALANCE", 0);  // whole rounds persistent + tail on 128x128: bitwise equal but
 // slower in the model (aggregator step 99.4-99.96 vs 98.7-99.0 ms, profiles/r10/ab_r10n_head_*.json), so off
+// key-split tail of the global attention launch (attention.hip, vggt_attention_fwd_ws): 0 the slot-model plan,
+// -1 off (bitwise the unsplit launch), parts | tail_blocks << 8 forced (tests, A/B).  Off by default: it is faster
+// (global attention 1,725 -> 1,679 us per launch, step -0.95 ms, profiles/r12/ab_attn_tail_split.md), but a row's
+// bits then depend on the launch's shape, and the grouped-encode and sequence parity tests require that a chunk
+// encoded in a batch of two equals the same chunk encoded alone
+int g_vggt_attn_tail_split = env_or("VGGT_ATTN_TAIL_SPLIT", -1);
 
 extern "C" int vggt_tune(int knob, int value) {
   int prev;
@@ -82,6 +88,11 @@ extern "C" int vggt_tune(int knob, int value) {
       if (value != 0 && value != 1) return VGGT_ERR_UNSUPPORTED;
       prev = g_vggt_gemm_balance;
       g_vggt_gemm_balance = value;
+      return prev;
+    case VGGT_TUNE_ATTN_TAIL_SPLIT:
+      if (value < -1 || (value > 0 && ((value & 0xff) < 2 || (value >> 8) < 1))) return VGGT_ERR_UNSUPPORTED;
+      prev = g_vggt_attn_tail_split;
+      g_vggt_attn_tail_split = value;
       return prev;
     case VGGT_TUNE_CONV_PF2:
       if (value != 0 && value != 1) return VGGT_ERR_UNSUPPORTED;
