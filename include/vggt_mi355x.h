@@ -540,7 +540,9 @@ int vggt_pose_compose(const float* chunk_sim3, const float* frame_se3, const flo
 
 /* Forward attention as vggt_attention_fwd (exact scores, no Q prescale) that
  * also stores lse[(b*heads + h)*nq + q] = log2 sum_k exp2(q.k * scale * log2 e),
- * consumed by vggt_attention_bwd (recompute of the frame blocks' SDPA). */
+ * consumed by vggt_attention_bwd (recompute of the frame blocks' SDPA).  o is
+ * normalised by the row sum of the bf16-rounded p that enter P.V (with one key
+ * o == v bit for bit); the lse is that of the unrounded p. */
 int vggt_attention_fwd_lse(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                            int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
                            int64_t o_bstride, float* lse, int batch, int heads, int nq, int nk, int D, float scale,

@@ -412,9 +412,11 @@ def headnorm_rope_out(src: torch.Tensor, dst: torch.Tensor, H: int, D: int, w, b
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, batch: int, heads: int, nq: int,
               nk: int, D: int, q_bstride: int, k_bstride: int, o_bstride: int, scale: Optional[float] = None,
-              tag: Optional[str] = None) -> None:
-    """q/k/v/o are 2-D row views whose column 0 is head 0's first element."""
+              tag: Optional[str] = None, v_bstride: Optional[int] = None) -> None:
+    """q/k/v/o are 2-D row views whose column 0 is head 0's first element;
+    v's batch stride (rows) defaults to k's."""
     _dev(q, "attention")
+    vbs = k_bstride if v_bstride is None else v_bstride
     sc = D ** -0.5 if scale is None else scale
     L = lib()
     # key-split tail of a long launch (vggt_attention_fwd_ws): the partials live in one
@@ -426,7 +428,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor
             ws = Workspace.get(q.device).buf("attn_tail_parts", 1, (nbytes + 3) // 4)
 
     def call():
-        return L.vggt_attention_fwd_ws(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), k_bstride,
+        return L.vggt_attention_fwd_ws(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), vbs,
                                        _p(o), _ld(o), o_bstride, batch, heads, nq, nk, D, float(sc), _p(ws), nbytes,
                                        _stream())
 
@@ -444,14 +446,17 @@ def attention_split_plan(batch: int, heads: int, nq: int, nk: int, D: int, cus: 
 
 
 def attention_stamps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, batch: int, heads: int,
-                     nq: int, nk: int, q_bstride: int, k_bstride: int, o_bstride: int) -> torch.Tensor:
+                     nq: int, nk: int, q_bstride: int, k_bstride: int, o_bstride: int,
+                     v_bstride: Optional[int] = None) -> torch.Tensor:
     """Diagnostic (vggt_attention_stamps): the default D = 64 forward with per-wave
-    s_memtime cycle sums of its tile segments; returns (nwg * NW, 8) int64."""
+    s_memtime cycle sums of its tile segments; returns (nwg * NW, 8) int64, sized for
+    the larger of the 4- and 8-wave grids (the library picks the form from
+    VGGT_TUNE_ATTN_WAVES; rows past the launched grid's nwg * NW stay zero)."""
     _dev(q, "attention_stamps")
-    nw = 8 if nq >= 4096 else 4
-    nwg = ((nq + nw * 32 - 1) // (nw * 32)) * heads * batch
-    st = torch.zeros(nwg * nw, 8, dtype=torch.int64, device=q.device)
-    rc = lib().vggt_attention_stamps(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), k_bstride,
+    rows = max(((nq + nw * 32 - 1) // (nw * 32)) * nw for nw in (4, 8)) * heads * batch
+    st = torch.zeros(rows, 8, dtype=torch.int64, device=q.device)
+    vbs = k_bstride if v_bstride is None else v_bstride
+    rc = lib().vggt_attention_stamps(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), vbs,
                                      _p(o), _ld(o), o_bstride, _p(st), batch, heads, nq, nk, float(64 ** -0.5),
                                      _stream())
     _check(rc, "vggt_attention_stamps")
@@ -852,20 +857,24 @@ def _train_ws(device, nbytes: int) -> torch.Tensor:
 
 
 def attention_fwd_lse(q, k, v, o, lse: torch.Tensor, batch: int, heads: int, nq: int, nk: int, D: int,
-                      q_bstride: int, k_bstride: int, o_bstride: int, scale: Optional[float] = None) -> None:
+                      q_bstride: int, k_bstride: int, o_bstride: int, scale: Optional[float] = None,
+                      v_bstride: Optional[int] = None) -> None:
     _dev(q, "attention_fwd_lse")
     assert lse.dtype == torch.float32 and lse.numel() >= batch * heads * nq
     sc = D ** -0.5 if scale is None else scale
-    rc = lib().vggt_attention_fwd_lse(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), k_bstride,
+    vbs = k_bstride if v_bstride is None else v_bstride
+    rc = lib().vggt_attention_fwd_lse(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), vbs,
                                       _p(o), _ld(o), o_bstride, _p(lse), batch, heads, nq, nk, D, float(sc), _stream())
     _check(rc, "vggt_attention_fwd_lse")
 
 
 def attention_bwd(q, k, v, o, do, lse, dq, dk, dv, batch: int, heads: int, nq: int, nk: int, D: int, q_bstride: int,
                   k_bstride: int, o_bstride: int, scale: Optional[float] = None) -> None:
-    """q/k/v/o/do/dq/dk/dv: 2-D bf16 row views; dk and dv share one leading dimension."""
+    """q/k/v/o/do/dq/dk/dv: 2-D bf16 row views; dk and dv share one leading dimension, and
+    so do o and do (the ABI has one ldo for both)."""
     _dev(q, "attention_bwd")
     assert _ld(dk) == _ld(dv)
+    assert _ld(do) == _ld(o)
     sc = D ** -0.5 if scale is None else scale
     delta = _train_ws(q.device, 4 * batch * heads * nq)
     rc = lib().vggt_attention_bwd(_p(q), _ld(q), q_bstride, _p(k), _ld(k), k_bstride, _p(v), _ld(v), _p(o), _p(do),

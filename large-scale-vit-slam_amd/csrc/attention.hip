@@ -246,6 +246,15 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   // -fno-honor-nans, so a NaN could slip past the range guard)
   constexpr float M_UNSET = -1e30f;
   float m_run = (VAR & 32) ? M_UNSET : -INFINITY, l_run = 0.f;
+  // VAR & 64 (the exact-score form, the training forward): a second row sum, over the
+  // bf16-rounded p that feed P.V, normalises O; l_run (unrounded p) stays the lse's.  At
+  // offset 0 the row's largest p = exp2(s) is no power of two, and its bf16 rounding
+  // (up to 2^-8) would not cancel against an unrounded sum: with one key, or one dominant
+  // key, O = v (1 + eps) for the whole row, and the backward's delta = dO . O leaves
+  // dO . v eps behind where dP - delta should cancel.  For the same reason this form
+  // takes the row max of its first tile as the offset whatever its size (p = 1 exactly at
+  // that key, as in a max-subtracting softmax), and so runs the shifted tile loop.
+  float lb_run = 0.f;
   f32x16 lsum = f32x16{};  // VAR & 8: every row of the ones-block product holds l[q]
   // VAR & 32: per-row bound exponent of the offset mode (60 at offset 0, THR
   // once the row carries a max offset) and whether every row of the wave sits
@@ -362,7 +371,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       // raw scores from LDS, take the true row max and move the offset of the
       // rows that need it -- before this tile's P.V (the textbook order).
       // VAR & 64: exact scores (s * c per element, no Q prescale).
-      float rs[4];
+      float rs[4], rb = 0.f;
       auto exps = [&](auto shc) {
         constexpr bool shifted = decltype(shc)::value;
 #pragma unroll
@@ -385,6 +394,17 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
               t[j] = (__bf16)p;
             }
             pf[kb][ss] = t;
+            if constexpr (VAR & 64) {
+              // v_dot2c_f32_bf16 against packed ones: one VALU per two rounded p
+              typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+              const bf16x2 ones = {(__bf16)1.0f, (__bf16)1.0f};
+              if (kb == 0 && ss == 0) rb = 0.f;
+#pragma unroll
+              for (int j = 0; j < 8; j += 2) {
+                const bf16x2 t2 = {t[j], t[j + 1]};
+                rb = __builtin_amdgcn_fdot2_f32_bf16(t2, ones, rb, false);
+              }
+            }
           }
       };
       // zero-offset loop (zc true): p = exp2(s); a wave that has left offset 0
@@ -412,7 +432,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         // for those rows (mx > m_run + lim - 5), so afterwards p <= 1 there and
         // every other row still has p <= 2^(lim-5), sum <= 2^lim
         float m_new = m_run;
-        if (m_run == M_UNSET) m_new = fabsf(mx) <= 60.f ? 0.f : mx;
+        if (m_run == M_UNSET) m_new = (!(VAR & 64) && fabsf(mx) <= 60.f) ? 0.f : mx;
         else if (mx > m_run + (lim - 5.f)) m_new = mx;
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
@@ -420,12 +440,14 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         limv = m_run == 0.f ? 0x1p60f : 256.0f;  // 2^lim
         zero_off = __builtin_amdgcn_ballot_w64(m_run != 0.f) == 0;
         l_run *= alpha;
+        if constexpr (VAR & 64) lb_run *= alpha;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) o[db] *= alpha;
         exps(std::true_type{});
         rsum = (rs[0] + rs[1]) + (rs[2] + rs[3]);
       }
       l_run += rsum;
+      if constexpr (VAR & 64) lb_run += rb;
     } else {
     // ---- row max (lane-partial over 32 keys, then the partner half)
     float mx;
@@ -745,7 +767,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       return;
     }
   }
-  const float inv = 1.f / l_run;
+  float inv = 1.f / l_run;
+  if constexpr ((VAR & 32) && (VAR & 64)) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lb_run), __float_as_uint(lb_run), false, false);
+    inv = 1.f / (__uint_as_float(sw[0]) + __uint_as_float(sw[1]));
+  }
   if constexpr (VAR & 1024) {
     VGGT_SEG(-1);
     st_acc[6] = st_prev;  // the wave's end (low 32 bits), to place it against the others of its workgroup
@@ -1429,7 +1455,9 @@ static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, con
 // Training recompute (alignment-head frame blocks under checkpoint, SURVEY §8f
 // row 4): the exact-score offset-free form (variant 96: no Q prescale, so the
 // backward's recomputed scores match bit for bit) that also stores the per-row
-// log2-sum-exp consumed by vggt_attention_bwd.
+// log2-sum-exp consumed by vggt_attention_bwd; its rows take their first tile's
+// max as the offset, O is normalised by the sum of the bf16-rounded p (lb_run),
+// the lse comes from the unrounded sum.
 // Diagnostic: the default forward (variant 33 -- 2081 in the 8-wave form unless
 // VGGT_ATTN_DMA_HALF=0 --, 32x32x16 form, the same 8- / 4-wave choice as
 // vggt_attention_fwd) with s_memtime segment stamps (VAR bit 1024).
