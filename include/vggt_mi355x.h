@@ -58,7 +58,13 @@ const char* vggt_version(void);
                                   9: persistent 256x256 ping-pong with register epilogue (bf16 / GELU / f32
                                   epilogues, N <= 4096; others as 7) */
 #define VGGT_TUNE_ATTN_WAVES 2 /* 2, 4 or 8 waves (64 / 128 / 256 query rows) per attention workgroup */
-#define VGGT_TUNE_ATTN_VARIANT 3 /* 0-15: attention instruction-schedule variant bits */
+#define VGGT_TUNE_ATTN_VARIANT 3 /* attention forward schedule, one of: 33 offset-free softmax (default), 32 the same
+                                    without hoisted K reads, 96 / 97 = 32 / 33 with exact scores, 3 / 7 / 11 / 15 the
+                                    max-tracking kernel (the other values below 16 are retired: VGGT_ERR_UNSUPPORTED),
+                                    19 / 23 pipelined QK^T, 161 = 33 on the 16x16x32 matrix-core form, 289 split-tile
+                                    pipeline, 545 DMA two tiles ahead, 2081 DMA from the priority half, 4129 no
+                                    priority raise (D = 64 forms: at D = 128 these run 33, and 19 / 23 run 3 / 7).
+                                    Env VGGT_ATTN_VARIANT (a value not listed here: the default) */
 #define VGGT_TUNE_CONV_PF2 4     /* split-bf16 conv gather: 1 two-deep (buffer loads, default), 0 one-deep */
 #define VGGT_TUNE_ATTN16 5       /* 1: D = 64 attention on the 16x16x32 matrix-core form, 0: 32x32x16 (default),
                                     2: 16x16x32 for 4-wave (nq < 4096) launches only */
@@ -267,6 +273,20 @@ int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const v
                           size_t ws_bytes, void* stream);
 size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream);
 int vggt_attention_split_plan(int batch, int heads, int nq, int nk, int D, int cus, int* tail_blocks, int* parts);
+
+/*
+ * Which forward kernel vggt_attention_fwd launches for (D, nq) under the current
+ * knobs (VGGT_TUNE_ATTN_VARIANT / _WAVES / ATTN16, env VGGT_ATTN_DMA_HALF): host
+ * arithmetic, no device call.  *form16: 1 the 16x16x32 kernel (*var is 0 then),
+ * 0 the 32x32x16 kernel with schedule bits *var (the variant's bits as run: 33
+ * resolves to 2081 on the 8-wave D = 64 path; the key-split bit of a
+ * vggt_attention_fwd_ws launch that splits is not included); *waves: waves per
+ * workgroup (2, 4 or 8).  Null pointers are skipped.  Returns VGGT_OK when the
+ * library holds that kernel, else VGGT_ERR_UNSUPPORTED (also for D not in {64, 128}).
+ */
+int vggt_attention_fwd_form(int D, int nq, int* form16, int* waves, int* var);
+/* The same for vggt_attention_stamps (D = 64, always the 32x32x16 kernel; *var includes the stamps bit 1024). */
+int vggt_attention_stamps_form(int nq, int* waves, int* var);
 
 /*
  * DINOv2 patch-embed input: ResNet-normalise fp32 images (F,3,H,W) and write

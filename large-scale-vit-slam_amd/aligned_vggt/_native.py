@@ -54,6 +54,8 @@ _SIGS = {
     "vggt_attention_fwd_ws": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i,
                               _f, _vp, ctypes.c_size_t, _vp],
     "vggt_attention_split_plan": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "vggt_attention_fwd_form": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "vggt_attention_stamps_form": [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_patch_im2col": [_vp, _i, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _i, _vp],
     "vggt_dino_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "vggt_special_tokens": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp],
@@ -443,6 +445,23 @@ def attention_split_plan(batch: int, heads: int, nq: int, nk: int, D: int, cus: 
     if not lib().vggt_attention_split_plan(batch, heads, nq, nk, D, cus, ctypes.byref(t), ctypes.byref(p)):
         return None
     return t.value, p.value
+
+
+def attention_fwd_form(D: int, nq: int):
+    """vggt_attention_fwd_form (host arithmetic only): (form16, waves, var, launchable) --
+    the forward kernel vggt_attention_fwd launches for (D, nq) under the current knobs, and
+    whether the library holds that kernel."""
+    f, w, v = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().vggt_attention_fwd_form(D, nq, ctypes.byref(f), ctypes.byref(w), ctypes.byref(v))
+    return f.value, w.value, v.value, rc == 0
+
+
+def attention_stamps_form(nq: int):
+    """vggt_attention_stamps_form (host arithmetic only): (waves, var, launchable) of the
+    kernel vggt_attention_stamps launches for nq under the current knobs."""
+    w, v = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().vggt_attention_stamps_form(nq, ctypes.byref(w), ctypes.byref(v))
+    return w.value, v.value, rc == 0
 
 
 def attention_stamps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, batch: int, heads: int,

@@ -26,7 +26,6 @@
 //  * XCD-aware block order: consecutive query blocks of one (batch, head)
 //    share an XCD so its K/V stream is served from one L2.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -56,7 +55,7 @@ struct AttnArgs {
   int batch, heads, nq, nk;
   float c;     // scale * log2(e)
   float* lse;  // optional [batch*heads*nq]: log2 sum exp2(scores * c) per row (training recompute)
-  // key-split tail (VAR & 8192 only): workgroups [0, n_full) are whole units (b, h, row block) in
+  // key-split tail (VAR & V_KEY_SPLIT only): workgroups [0, n_full) are whole units (b, h, row block) in
   // linear order; the units from n_full on run as `parts` workgroups each, part p over the keys
   // [p * part_tiles * 64, ...) (the last part takes the rest), and leave (m, l, O) in ws
   int n_full, parts, part_tiles;
@@ -104,14 +103,36 @@ __device__ __forceinline__ int v_swz(int row, int chunk) {
   else return chunk ^ ((row & 3) << 2);
 }
 
-// VAR (schedule variants, A/B-tested through vggt_tune): bit 0 = all K
-// fragment reads before the QK^T MFMAs, bit 1 = four-chain row max, bit 2 =
-// four partial row sums, bit 3 = row sums on the matrix core (an all-ones
-// V^T block times P^T: 4 extra MFMAs per tile replace 32 VALU adds per lane;
-// the sum is then over the bf16-rounded P that also feeds P.V).  Bit 10
-// (1024, diagnostic, on top of 33): s_memtime stamps per tile segment, summed
-// per wave into a.lse reinterpreted as unsigned long long[nwg][NW][STAMP_N]
-// (vggt_attention_stamps; the kernel writes no lse then).
+// VAR: the schedule bits of attn_fwd_kernel (A/B-tested through vggt_tune).  A kernel is a (D, NW, VAR) triple of
+// VGGT_ATTN_KERNELS; attn_resolve maps the knobs to one.  The values are part of the kernels' mangled names.
+constexpr int V_HOIST_K = 1;       // all K fragment reads before the QK^T MFMAs
+constexpr int V_MAX4 = 2;          // max-tracking form: four-chain row max
+constexpr int V_SUM4 = 4;          // max-tracking form: four partial row sums
+constexpr int V_MFMA_SUM = 8;      // max-tracking form: row sums on the matrix core (an all-ones V^T block times P^T:
+                                   // 4 MFMAs per tile replace 32 VALU adds per lane), over the bf16-rounded P of P.V
+constexpr int V_PIPE_QK = 16;      // QK^T of tile t+1 issued before tile t's softmax (3 K|V slots; max-tracking form)
+constexpr int V_OFFSET_FREE = 32;  // offset-free online softmax (soft_pv): no row max on the common path
+constexpr int V_EXACT = 64;        // offset-free with exact scores: s * c per element instead of the Q prescale, O
+                                   // normalised by the sum of the bf16-rounded p (the training forward)
+constexpr int V_SPLIT_TILE = 256;  // offset-free, full tiles as two software-pipelined 32-key halves (tile_split)
+constexpr int V_DMA_AHEAD = 512;   // offset-free, 3 K|V slots, LDS-DMA two tiles ahead
+constexpr int V_STAMPS = 1024;     // diagnostic (vggt_attention_stamps): s_memtime stamps per tile segment, summed per
+                                   // wave into a.lse as unsigned long long[nwg][NW][STAMP_N]; the kernel writes no lse
+constexpr int V_DMA_HALF = 2048;   // 8-wave form: only the priority half (waves 4-7) issues the LDS-DMA
+constexpr int V_NO_PRIO = 4096;    // 8-wave form: no priority raise for waves 4-7
+constexpr int V_KEY_SPLIT = 8192;  // key-split tail: workgroups past n_full run one key range of a tail unit each
+// The public variant ids (VGGT_TUNE_ATTN_VARIANT) are these bits OR'd; 128 is no kernel bit, only the 16x16x32 form's id
+constexpr int ID_FORM16 = 128;
+constexpr int V_33 = V_OFFSET_FREE | V_HOIST_K;  // the default
+constexpr int V_96 = V_OFFSET_FREE | V_EXACT;    // the training forward (vggt_attention_fwd_lse)
+constexpr int V_161 = V_33 | ID_FORM16;
+constexpr int V_289 = V_33 | V_SPLIT_TILE;
+constexpr int V_545 = V_33 | V_DMA_AHEAD;
+constexpr int V_2081 = V_33 | V_DMA_HALF;
+constexpr int V_4129 = V_33 | V_NO_PRIO;
+constexpr int V_19 = V_PIPE_QK | V_MAX4 | V_HOIST_K;
+constexpr int V_23 = V_19 | V_SUM4;
+constexpr int V_LEGACY = V_HOIST_K | V_MAX4 | V_SUM4 | V_MFMA_SUM;  // the max-tracking form's own bits (3, 7, 11, 15)
 constexpr int STAMP_N = 8;
 template <int D, int NW, int VAR>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
@@ -123,7 +144,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   constexpr int RPI = 1024 / ROWB;       // rows per 1-KiB DMA instruction
   constexpr int CPR = ROWB / 16;         // 16-B chunks per row
   constexpr int IPW = TILEB / 1024 / NW;  // DMA instructions per wave per operand
-  constexpr int NSLOT = (VAR & (16 | 512)) ? 3 : 2;  // K|V tile slots (3: pipelined QK^T / DMA two ahead)
+  constexpr int NSLOT = (VAR & (V_PIPE_QK | V_DMA_AHEAD)) ? 3 : 2;  // K|V tile slots (3: pipelined QK^T / DMA two ahead)
   __shared__ __attribute__((aligned(16))) char smem[NSLOT * 2 * TILEB];
 
   const int lane = threadIdx.x & 63;
@@ -132,16 +153,16 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   // 8-wave form: the second-dispatched half (waves 4-7) shares each SIMD with
   // an older wave and loses VALU arbitration on every segment; one static
   // priority raise for it (cdna_hip_programming.md T5, static form).
-  // (VAR & 4096: no priority raise -- re-measured with the segment stamps, r11)
-  if constexpr (NW == 8 && !(VAR & 4096)) {
+  // (VAR & V_NO_PRIO: no priority raise -- re-measured with the segment stamps, r11)
+  if constexpr (NW == 8 && !(VAR & V_NO_PRIO)) {
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
   }
   const int nqb = (a.nq + BQ - 1) / BQ;
-  // VAR & 8192 (key-split tail): the first n_full workgroups are whole units,
+  // VAR & V_KEY_SPLIT (key-split tail): the first n_full workgroups are whole units,
   // the others one part of a tail unit each -- its keys [key0, key0 + nk); the
   // XCD remap runs within either range (dispatch follows the block index, so
   // the whole units keep the low indices)
-  constexpr bool SPLIT = (VAR & 8192) != 0;
+  constexpr bool SPLIT = (VAR & V_KEY_SPLIT) != 0;
   int bid, nk = a.nk, key0 = 0, slab = -1;
   if constexpr (SPLIT) {
     const int bx = blockIdx.x;
@@ -172,7 +193,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   bf16x8 qf[NKS];
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const bf16x8*)(qp + (int64_t)qr * a.ldq + ks * 16 + 8 * hl);
-  if constexpr ((VAR & 32) && !(VAR & 64)) {
+  if constexpr ((VAR & V_OFFSET_FREE) && !(VAR & V_EXACT)) {
     // scores come out of the MFMA already in log2 units: Q * (scale log2 e),
     // re-rounded to bf16 (one extra rounding of Q, ~2^-9 relative)
 #pragma unroll
@@ -184,12 +205,12 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[ks]));  // retire the Q loads before the loop
 
   // ---- loop-invariant DMA offsets and LDS destinations
-  // VAR & 2048 (8-wave form): only the priority-1 half (waves 4-7) issues the
-  // tile's LDS-DMA, two pieces per operand each.  Segment stamps (VAR & 1024,
+  // VAR & V_DMA_HALF (8-wave form): only the priority-1 half (waves 4-7) issues the
+  // tile's LDS-DMA, two pieces per operand each.  Segment stamps (VAR & V_STAMPS,
   // profiles/r11) showed those waves finish each tile ~870 cycles before their
   // SIMD partners and wait at the barrier, while the partners' tile work is the
   // tile's critical path: the DMA issue moves off it.
-  constexpr bool DMAH = (VAR & 2048) && NW == 8;
+  constexpr bool DMAH = (VAR & V_DMA_HALF) && NW == 8;
   constexpr int IPWX = DMAH ? 2 * IPW : IPW;  // pieces per issuing wave per operand
   const int pbase = DMAH ? (wave >= 4 ? wave - 4 : 0) * IPWX : wave * IPW;
   uint32_t koff[IPWX], voff[IPWX];
@@ -241,12 +262,12 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   f32x16 o[NDB];
 #pragma unroll
   for (int i = 0; i < NDB; ++i) o[i] = f32x16{};
-  // VAR & 32 starts from a finite "unset" offset: masked scores (-inf) minus
+  // VAR & V_OFFSET_FREE starts from a finite "unset" offset: masked scores (-inf) minus
   // it stay -inf (-inf - -inf would be a NaN, and the kernel is built with
   // -fno-honor-nans, so a NaN could slip past the range guard)
   constexpr float M_UNSET = -1e30f;
-  float m_run = (VAR & 32) ? M_UNSET : -INFINITY, l_run = 0.f;
-  // VAR & 64 (the exact-score form, the training forward): a second row sum, over the
+  float m_run = (VAR & V_OFFSET_FREE) ? M_UNSET : -INFINITY, l_run = 0.f;
+  // VAR & V_EXACT (the exact-score form, the training forward): a second row sum, over the
   // bf16-rounded p that feed P.V, normalises O; l_run (unrounded p) stays the lse's.  At
   // offset 0 the row's largest p = exp2(s) is no power of two, and its bf16 rounding
   // (up to 2^-8) would not cancel against an unrounded sum: with one key, or one dominant
@@ -255,15 +276,15 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   // takes the row max of its first tile as the offset whatever its size (p = 1 exactly at
   // that key, as in a max-subtracting softmax), and so runs the shifted tile loop.
   float lb_run = 0.f;
-  f32x16 lsum = f32x16{};  // VAR & 8: every row of the ones-block product holds l[q]
-  // VAR & 32: per-row bound exponent of the offset mode (60 at offset 0, THR
+  f32x16 lsum = f32x16{};  // VAR & V_MFMA_SUM: every row of the ones-block product holds l[q]
+  // VAR & V_OFFSET_FREE: per-row bound exponent of the offset mode (60 at offset 0, THR
   // once the row carries a max offset) and whether every row of the wave sits
   // at offset 0 (then p = exp2(s) with no subtraction at all)
   float lim = THR, limv = 256.0f;
   bool zero_off = false;
   const float c = a.c;
   const int nt = (nk + BKV - 1) / BKV;
-  // VAR & 1024: per-wave cycle sums of the tile segments (s_memtime, one scalar
+  // VAR & V_STAMPS: per-wave cycle sums of the tile segments (s_memtime, one scalar
   // statement with its lgkmcnt(0)); 32-bit sums, no tile counter (the host
   // knows the tile count): so instrumented, the kernel keeps the default's 113
   // VGPRs and occupancy (a per-tile counter, VGPR-pinned sums or scheduling
@@ -271,7 +292,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   uint32_t st_acc[STAMP_N] = {}, st_prev = 0;
 #define VGGT_SEG(i)                                                                                  \
   do {                                                                                               \
-    if constexpr (VAR & 1024) {                                                                      \
+    if constexpr (VAR & V_STAMPS) {                                                                  \
       /* no sched_barrier: it pushed the kernel to 150 VGPRs */                                     \
       unsigned long long now_;                                                                       \
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");                     \
@@ -289,7 +310,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     constexpr int BUF = decltype(bufc)::value;
     const char* base = smem + BUF * 2 * TILEB;
     f32x16 s[2];
-    if constexpr (VAR & 1) {
+    if constexpr (VAR & V_HOIST_K) {
       // all K fragment reads first, then the two 32-key accumulator chains
       // interleaved (no MFMA waits on a just-issued LDS read)
       bf16x8 kf[2][NKS];
@@ -317,7 +338,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     }
     return S2{{s[0], s[1]}};
   };
-  // ---- the same scores recomputed on a rare path (VAR & 32): the LDS offset
+  // ---- the same scores recomputed on a rare path (VAR & V_OFFSET_FREE): the LDS offset
   // goes through an empty asm so the reads are not CSE'd with the common
   // path's (which would keep 32 K-fragment registers live across the tile)
   // and the MFMAs cannot be speculated out of the branch
@@ -338,6 +359,15 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     }
     return S2{{s[0], s[1]}};
   };
+  // ---- O^T[db] += V^T . P^T over the 16 keys from `row` of the V tile behind `base`
+  auto pv16 = [&](const char* base, int db, int row, const bf16x8& p) {
+    const char* p0 = base + va[db] + row * ROWB;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0));
+    const s16x4 hi =
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0 + 8 * ROWB));
+    const bf16x8 vf = __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, p, o[db], 0, 0, 0);
+  };
   // ---- mask, online softmax and O^T += V^T . P^T for the tile in slot BUF
   auto soft_pv = [&](auto bufc, int t, S2 sc, auto zc) {
     constexpr int BUF = decltype(bufc)::value;
@@ -357,7 +387,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     };
     mask();
     bf16x8 pf[2][2];
-    if constexpr (VAR & 32) {
+    if constexpr (VAR & V_OFFSET_FREE) {
       // Offset-free online softmax.  softmax is shift-invariant, and bf16 / fp32
       // keep their relative precision at any exponent, so the max subtraction
       // only guards the exponent range.  Each row carries an offset m_run
@@ -370,7 +400,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       // bound (first tile: m_run = -inf -> p = inf) does the wave recompute the
       // raw scores from LDS, take the true row max and move the offset of the
       // rows that need it -- before this tile's P.V (the textbook order).
-      // VAR & 64: exact scores (s * c per element, no Q prescale).
+      // VAR & V_EXACT: exact scores (s * c per element, no Q prescale).
       float rs[4], rb = 0.f;
       auto exps = [&](auto shc) {
         constexpr bool shifted = decltype(shc)::value;
@@ -384,7 +414,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               float x = s[kb][8 * ss + j];
-              if constexpr (VAR & 64) x = shifted ? fmaf(x, c, -m_run) : x * c;
+              if constexpr (VAR & V_EXACT) x = shifted ? fmaf(x, c, -m_run) : x * c;
               else if constexpr (shifted) x -= m_run;
               const float p = __builtin_amdgcn_exp2f(x);
               // one chain: split sums get SLP-packed into v_pk_add_f32; started from the
@@ -394,7 +424,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
               t[j] = (__bf16)p;
             }
             pf[kb][ss] = t;
-            if constexpr (VAR & 64) {
+            if constexpr (VAR & V_EXACT) {
               // v_dot2c_f32_bf16 against packed ones: one VALU per two rounded p
               typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
               const bf16x2 ones = {(__bf16)1.0f, (__bf16)1.0f};
@@ -427,12 +457,12 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(mx, s[1][r]), s[1][r + 1]);
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
         mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        if constexpr (VAR & 64) mx *= c;
+        if constexpr (VAR & V_EXACT) mx *= c;
         // a lane sum > 2^lim implies a p > 2^(lim-5): move the offset exactly
         // for those rows (mx > m_run + lim - 5), so afterwards p <= 1 there and
         // every other row still has p <= 2^(lim-5), sum <= 2^lim
         float m_new = m_run;
-        if (m_run == M_UNSET) m_new = (!(VAR & 64) && fabsf(mx) <= 60.f) ? 0.f : mx;
+        if (m_run == M_UNSET) m_new = (!(VAR & V_EXACT) && fabsf(mx) <= 60.f) ? 0.f : mx;
         else if (mx > m_run + (lim - 5.f)) m_new = mx;
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
@@ -440,18 +470,18 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         limv = m_run == 0.f ? 0x1p60f : 256.0f;  // 2^lim
         zero_off = __builtin_amdgcn_ballot_w64(m_run != 0.f) == 0;
         l_run *= alpha;
-        if constexpr (VAR & 64) lb_run *= alpha;
+        if constexpr (VAR & V_EXACT) lb_run *= alpha;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) o[db] *= alpha;
         exps(std::true_type{});
         rsum = (rs[0] + rs[1]) + (rs[2] + rs[3]);
       }
       l_run += rsum;
-      if constexpr (VAR & 64) lb_run += rb;
+      if constexpr (VAR & V_EXACT) lb_run += rb;
     } else {
     // ---- row max (lane-partial over 32 keys, then the partner half)
     float mx;
-    if constexpr (VAR & 2) {
+    if constexpr (VAR & V_MAX4) {
       // four independent v_max3 chains (built with -fno-honor-nans), merged:
       // dependency depth 5 instead of 16
       float mc[4];
@@ -481,7 +511,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       const float m_new = fmaxf(m_run, mx);
       const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
       m_run = m_new;
-      if constexpr (VAR & 8) lsum *= alpha;
+      if constexpr (VAR & V_MFMA_SUM) lsum *= alpha;
       else l_run *= alpha;
 #pragma unroll
       for (int db = 0; db < NDB; ++db) o[db] *= alpha;
@@ -494,10 +524,10 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float p = __builtin_amdgcn_exp2f(fmaf(s[kb][8 * ss + j], c, -m_run));
-          if constexpr (!(VAR & 8)) rs[(VAR & 4) ? 2 * kb + ss : 0] += p;
+          if constexpr (!(VAR & V_MFMA_SUM)) rs[(VAR & V_SUM4) ? 2 * kb + ss : 0] += p;
           pf[kb][ss][j] = (__bf16)p;
         }
-    if constexpr (!(VAR & 8)) l_run += (rs[0] + rs[1]) + (rs[2] + rs[3]);
+    if constexpr (!(VAR & V_MFMA_SUM)) l_run += (rs[0] + rs[1]) + (rs[2] + rs[3]);
     }
     // ---- O^T += V^T . P^T
 #pragma unroll
@@ -505,15 +535,8 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-          const char* p0 = base + va[db] + (kb * 32 + 16 * ss) * ROWB;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0));
-          const s16x4 hi =
-              __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0 + 8 * ROWB));
-          const bf16x8 vf = __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-          o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kb][ss], o[db], 0, 0, 0);
-        }
-    if constexpr (VAR & 8) {
+        for (int ss = 0; ss < 2; ++ss) pv16(base, db, kb * 32 + 16 * ss, pf[kb][ss]);
+    if constexpr (VAR & V_MFMA_SUM) {
       bf16x8 ones;
 #pragma unroll
       for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
@@ -524,7 +547,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     }
   };
 
-  // ---- VAR & 256 (offset-free only; full tiles): the tile as two 32-key
+  // ---- VAR & V_SPLIT_TILE (offset-free only; full tiles): the tile as two 32-key
   // halves, software-pipelined inside the wave -- the QK^T MFMAs of half 1
   // are issued between the exps of half 0, and the P.V MFMAs of half 0
   // between the exps of half 1, so a wave keeps its own matrix pipe busy
@@ -573,14 +596,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int db = 0; db < NDB; ++db)
 #pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-          const char* p0_ = base + va[db] + (kb * 32 + 16 * ss) * ROWB;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0_));
-          const s16x4 hi =
-              __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)LDS_PTR(p0_ + 8 * ROWB));
-          const bf16x8 vf = __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-          o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ss], o[db], 0, 0, 0);
-        }
+        for (int ss = 0; ss < 2; ++ss) pv16(base, db, kb * 32 + 16 * ss, pf[ss]);
     };
     auto rowmax = [&](const f32x16& a0, const f32x16* a1) {
       float mx = fmaxf(a0[0], a0[1]);
@@ -637,7 +653,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>;
 
-  if constexpr (VAR & 16) {
+  if constexpr (VAR & V_PIPE_QK) {
     // Pipelined: the QK^T MFMAs of tile t+1 are issued before tile t's softmax
     // (T15), so the matrix pipe works while the VALU does exp / max / cvt.
     // 3 slots: t (V read by P.V), t+1 (K read by QK^T), t+2 (DMA in flight,
@@ -665,7 +681,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       if (t + 2 >= nt) break;
       step(I2{}, I0{}, I1{}, t + 2);
     }
-  } else if constexpr (VAR & 512) {
+  } else if constexpr (VAR & V_DMA_AHEAD) {
     // Three K|V slots, the DMA two tiles ahead: tile t+2 is staged at the start
     // of tile t (into the slot tile t-1 used, retired by the barrier that ended
     // tile t-1), and the end of tile t waits only for tile t+1's pieces
@@ -703,11 +719,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    // VAR & 32: two copies of the tile loop, one per offset mode (one loop with
+    // VAR & V_OFFSET_FREE: two copies of the tile loop, one per offset mode (one loop with
     // a per-tile choice between the two exp forms costs ~25 VGPRs at the merge:
     // occupancy 4 -> 3).  Every wave starts in the zero-offset loop and leaves
     // it for good, at a tile pair boundary, once one of its rows took an offset.
-    // VAR & 1024 segments of one tile: [2] the tile's work (DMA issue, QK^T, softmax,
+    // VAR & V_STAMPS segments of one tile: [2] the tile's work (DMA issue, QK^T, softmax,
     // P.V issue, up to its last LDS read), [3] end-of-tile vmcnt(0) wait for the next
     // tile's DMA, [4] barrier.  (Stamps inside the tile body, between the
     // DMA issue and QK^T or between the softmax and P.V, serialise what the compiler
@@ -716,7 +732,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       for (int t = t0; t < nt; t += 2) {
         VGGT_SEG(-1);
         if (t + 1 < nt) stage(1, t + 1);
-        if ((VAR & 256) && (t + 1) * BKV <= nk) tile_split(I0{}, zc);
+        if ((VAR & V_SPLIT_TILE) && (t + 1) * BKV <= nk) tile_split(I0{}, zc);
         else soft_pv(I0{}, t, qk(I0{}), zc);
         VGGT_SEG(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -725,7 +741,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
         VGGT_SEG(4);
         if (t + 1 >= nt) break;
         if (t + 2 < nt) stage(0, t + 2);
-        if ((VAR & 256) && (t + 2) * BKV <= nk) tile_split(I1{}, zc);
+        if ((VAR & V_SPLIT_TILE) && (t + 2) * BKV <= nk) tile_split(I1{}, zc);
         else soft_pv(I1{}, t + 1, qk(I1{}), zc);
         VGGT_SEG(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -738,7 +754,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
       }
       return nt;
     };
-    if constexpr (VAR & 32) {
+    if constexpr (VAR & V_OFFSET_FREE) {
       const int t1 = run(std::true_type{}, 0);
       if (t1 < nt) run(std::false_type{}, t1);
     } else {
@@ -747,7 +763,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   }
 
   // ---- epilogue: normalise, O[q][d] bf16
-  if constexpr (VAR & 8) {
+  if constexpr (VAR & V_MFMA_SUM) {
     l_run = lsum[0];
   } else {
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
@@ -768,11 +784,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
     }
   }
   float inv = 1.f / l_run;
-  if constexpr ((VAR & 32) && (VAR & 64)) {
+  if constexpr ((VAR & V_OFFSET_FREE) && (VAR & V_EXACT)) {
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lb_run), __float_as_uint(lb_run), false, false);
     inv = 1.f / (__uint_as_float(sw[0]) + __uint_as_float(sw[1]));
   }
-  if constexpr (VAR & 1024) {
+  if constexpr (VAR & V_STAMPS) {
     VGGT_SEG(-1);
     st_acc[6] = st_prev;  // the wave's end (low 32 bits), to place it against the others of its workgroup
     if (lane == 0) {
@@ -1076,7 +1092,7 @@ __global__ __launch_bounds__(NW * 64, 16 / NW) void attn16_fwd_kernel(AttnArgs a
 }
 
 // ---------------------------------------------------------------------------
-// Merge of the key-split tail (attn_fwd_kernel, VAR & 8192): for every row of
+// Merge of the key-split tail (attn_fwd_kernel, VAR & V_KEY_SPLIT): for every row of
 // the tail units, over its parts in index order (a fixed order: bitwise stable
 // from run to run), M = max m_i, o = sum 2^(m_i - M) O_i / sum 2^(m_i - M) l_i,
 // rounded to bf16 into the caller's o.  One thread per float4 of a partial, in
@@ -1278,178 +1294,193 @@ void tail_split_of(int batch, int heads, int nq, int nk, int cus, int* tail, int
   *part_tiles = pt;
 }
 
-bool attn_split_path(int nq, int D) {
-  static const bool dma_half = getenv("VGGT_ATTN_DMA_HALF") ? atoi(getenv("VGGT_ATTN_DMA_HALF")) != 0 : true;
-  return dma_half && g_vggt_attn_variant == 33 && D == 64 && g_vggt_attn_waves == 8 && nq >= 4096;
-}
-}  // namespace
+// ---- which kernel a launch runs -------------------------------------------
+struct AttnForm {
+  bool form16;     // attn16_fwd_kernel<nw> (var 0: it has no schedule bits), else attn_fwd_kernel<D, nw, var>
+  int nw, var;
+  bool key_split;  // the one form whose launch may take the key-split tail (var | V_KEY_SPLIT)
+};
 
-extern "C" size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream) {
-  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !attn_split_path(nq, D)) return 0;
-  int tail, parts, pt;
-  tail_split_of(batch, heads, nq, nk, attn_cu_count((hipStream_t)stream), &tail, &parts, &pt);
-  return (size_t)tail * parts * SPLIT_SLAB * sizeof(float);
-}
-
-static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
-                              int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
-                              int64_t o_bstride, int batch, int heads, int nq, int nk, int D, float scale, void* ws,
-                              size_t ws_bytes, void* stream);
-
-extern "C" int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
-                                  int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
-                                  int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
-                                  float scale, void* stream) {
-  return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
-                            nq, nk, D, scale, nullptr, 0, stream);
-}
-
-// vggt_attention_fwd with a workspace: the only entry that may run the last,
-// partial round of workgroups of the 8-wave D = 64 default path split over the
-// keys (vggt_attention_ws_bytes says how much it needs for this shape under
-// the current VGGT_TUNE_ATTN_TAIL_SPLIT; with ws == NULL it never splits).
-extern "C" int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
-                                     int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
-                                     int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
-                                     float scale, void* ws, size_t ws_bytes, void* stream) {
-  if (ws && (uintptr_t)ws % 16) return VGGT_ERR_ALIGN;
-  return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
-                            nq, nk, D, scale, ws, ws_bytes, stream);
+// The one place that maps the knobs to a kernel: (public variant id, VGGT_TUNE_ATTN_WAVES,
+// VGGT_TUNE_ATTN16, VGGT_ATTN_DMA_HALF, D, nq) -> form.  Pure arithmetic, first match wins.
+AttnForm attn_resolve(int variant, int waves, int attn16, int dma_half, int D, int nq) {
+  // 8-wave workgroups (256 query rows) for long sequences; 4-wave ones (128 rows) when the query count is short
+  // enough that the padding of a 256-row block would cost more than the pairing gains; 2-wave ones (64 rows) for grids
+  // that fill a fraction of one round of slots -- only ids that reduce to 33 below (hoisted K, offset-free, not exact)
+  const bool two_ok = (variant & V_OFFSET_FREE) && (variant & (V_EXACT | V_HOIST_K)) == V_HOIST_K;
+  const int nw = (waves == 8 && nq >= 4096) ? 8 : (waves == 2 && two_ok) ? 2 : 4;
+  const bool d64 = D == 64, wide = d64 && nw != 2;  // the special forms below are D = 64 only, most 4 / 8 waves only
+  // 16x16x32 matrix-core form: 161 forces it; 33 takes it with VGGT_ATTN16=1, or =2 (default) for the 4-wave
+  // (nq < 4096: frame / DINOv2) launches only.  All launches: faster back to back in kbench (profiles/r6c: global 1.80
+  // vs 1.83 ms, frame 128-134 vs 135-137 us) but not in the model (r6d: global 1.87 vs 1.84 ms, step 100.8 vs 100.5 ms)
+  if (wide && (variant == V_161 || (variant == V_33 && (attn16 == 1 || (attn16 == 2 && nw == 4)))))
+    return {true, nw, 0, false};
+  if (d64 && (variant == V_19 || variant == V_23)) return {false, nw, variant, false};  // (never 2 waves: not two_ok)
+  // Default (round 6): the 8-wave D = 64 form of 33 issues its LDS-DMA from the priority half only (2081): global
+  // attention 1,858-1,860 -> 1,814-1,819 us, aggregator step 97.66-97.75 -> 96.56-97.21 ms, interleaved on one box
+  // (profiles/r11/ab_attn_dma_half.md).  VGGT_ATTN_DMA_HALF=0: every wave issues its piece.
+  if (d64 && nw == 8 && variant == V_33 && dma_half) return {false, 8, V_2081, true};
+  // 2081 / 4129 differ from 33 in the 8-wave form only
+  if (wide && (variant == V_2081 || variant == V_4129)) return {false, nw, nw == 8 ? variant : V_33, false};
+  if (wide && (variant == V_545 || variant == V_289)) return {false, nw, variant, false};
+  // Every other offset-free launch keeps the hoist and exact-score bits alone: 32 / 33 / 96 / 97
+  // as they are, and 161 / 289 / 545 / 2081 / 4129 run 33 at D = 128 and in 2-wave groups
+  // (their own forms are D = 64, 4 / 8 waves; two_ok admits exactly the ids that land on 33 here)
+  if (variant & V_OFFSET_FREE) return {false, nw, variant & (V_OFFSET_FREE | V_EXACT | V_HOIST_K), false};
+  // The max-tracking form: 3 / 7 / 11 / 15, and 19 / 23 at D = 128 (no 3-slot form there) run 3 / 7
+  return {false, nw, variant & V_LEGACY, false};
 }
 
-static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
-                              int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,
-                              int64_t o_bstride, int batch, int heads, int nq, int nk, int D, float scale, void* ws,
-                              size_t ws_bytes, void* stream) {
+AttnForm attn_resolve_now(int D, int nq) {
+  return attn_resolve(g_vggt_attn_variant, g_vggt_attn_waves, g_vggt_attn16, g_vggt_attn_dma_half, D, nq);
+}
+
+// Every attn_fwd_kernel the library holds, as X(D, NW, VAR)
+#define VGGT_ATTN_D_NW(X, V) X(64, 4, V) X(64, 8, V) X(128, 4, V) X(128, 8, V)
+#define VGGT_ATTN_KERNELS(X)                                                                              \
+  VGGT_ATTN_D_NW(X, V_HOIST_K | V_MAX4) VGGT_ATTN_D_NW(X, V_HOIST_K | V_MAX4 | V_SUM4)                    \
+  VGGT_ATTN_D_NW(X, V_HOIST_K | V_MAX4 | V_MFMA_SUM) VGGT_ATTN_D_NW(X, V_LEGACY)                          \
+  VGGT_ATTN_D_NW(X, V_OFFSET_FREE) VGGT_ATTN_D_NW(X, V_33)                                                \
+  VGGT_ATTN_D_NW(X, V_96) VGGT_ATTN_D_NW(X, V_96 | V_HOIST_K)                                             \
+  X(64, 2, V_33) X(128, 2, V_33)                                                                          \
+  X(64, 4, V_19) X(64, 8, V_19) X(64, 4, V_23) X(64, 8, V_23)                                             \
+  X(64, 4, V_289) X(64, 8, V_289) X(64, 4, V_545) X(64, 8, V_545)                                         \
+  X(64, 8, V_2081) X(64, 8, V_2081 | V_KEY_SPLIT) X(64, 8, V_4129)                                        \
+  X(64, 4, V_33 | V_STAMPS) X(64, 8, V_33 | V_STAMPS) X(64, 8, V_2081 | V_STAMPS) X(64, 8, V_4129 | V_STAMPS)
+
+// Whether the library holds the kernel of form `f`
+bool attn_has(const AttnForm& f, int D) {
+  if (f.form16) return D == 64 && (f.nw == 4 || f.nw == 8);
+#define VGGT_ATTN_IS(DD, NWW, V) \
+  if (D == DD && f.nw == NWW && f.var == (V)) return true;
+  VGGT_ATTN_KERNELS(VGGT_ATTN_IS)
+#undef VGGT_ATTN_IS
+  return false;
+}
+
+// Launches the kernel of form `f` on `grid` workgroups (VGGT_ERR_UNSUPPORTED: the library does not hold it)
+int attn_launch(const AttnForm& f, int D, const AttnArgs& a, int grid, hipStream_t s) {
+  if (!attn_has(f, D)) return VGGT_ERR_UNSUPPORTED;
+  if (f.form16) {
+    if (f.nw == 8) attn16_fwd_kernel<8><<<grid, 512, 0, s>>>(a);
+    else attn16_fwd_kernel<4><<<grid, 256, 0, s>>>(a);
+  }
+#define VGGT_ATTN_TRY(DD, NWW, V) \
+  else if (D == DD && f.nw == NWW && f.var == (V)) attn_fwd_kernel<DD, NWW, (V)><<<grid, NWW * 64, 0, s>>>(a);
+  VGGT_ATTN_KERNELS(VGGT_ATTN_TRY)
+#undef VGGT_ATTN_TRY
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+// The stamped form (vggt_attention_stamps): always D = 64 on the 32x32x16 kernel (VGGT_TUNE_ATTN16
+// is ignored), 2 waves taken as 4.  In the 8-wave form 2081 when the variant is 2081, or is 33 with
+// dma_half; 4129 when it is 4129; 33 for every other variant.  In the 4-wave form always 33.
+AttnForm attn_resolve_stamps(int variant, int waves, int dma_half, int nq) {
+  const int v = (variant == V_2081 || variant == V_4129) ? variant : V_33;
+  AttnForm f = attn_resolve(v, waves == 2 ? 4 : waves, 0, variant == V_33 && dma_half, 64, nq);
+  f.var |= V_STAMPS;
+  return f;
+}
+
+// The checks and the kernel arguments every forward entry shares (lse: see AttnArgs)
+int attn_args(AttnArgs* a, const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+              int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo, int64_t o_bstride,
+              int batch, int heads, int nq, int nk, int D, float scale, float* lse) {
   if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0) return VGGT_ERR_SHAPE;
   if (D != 64 && D != 128) return VGGT_ERR_UNSUPPORTED;
   if ((ldq | ldk | ldv | ldo) % 8 || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16)
     return VGGT_ERR_ALIGN;
   // 32-bit DMA offsets and descriptor arithmetic: K / V of one (batch, head) must span < 2 GiB
   if ((uint64_t)nk * (uint64_t)(ldk > ldv ? ldk : ldv) * 2 >= (1ull << 31)) return VGGT_ERR_SHAPE;
-  AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
-             q_bstride, k_bstride, v_bstride, o_bstride, batch, heads, nq, nk,
-             scale * 1.4426950408889634f, nullptr};
-  // 8-wave workgroups (256 query rows) for long sequences; 4-wave ones
-  // (128 rows) when the query count is short enough that the padding of a
-  // 256-row block would cost more than the pairing gains.
-  // 2-wave workgroups (64 query rows; only the default offset-free variant 33
-  // is instantiated) for grids that fill a fraction of one round of slots.
-  const bool two_ok = (g_vggt_attn_variant & 32) && (g_vggt_attn_variant & 65) == 1;
-  const int nw = (g_vggt_attn_waves == 8 && nq >= 4096) ? 8 : (g_vggt_attn_waves == 2 && two_ok) ? 2 : 4;
-  const int nwg = ((nq + nw * 32 - 1) / (nw * 32)) * heads * batch;
+  *a = AttnArgs{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
+                q_bstride, k_bstride, v_bstride, o_bstride, batch, heads, nq, nk,
+                scale * 1.4426950408889634f, lse};
+  return VGGT_OK;
+}
+
+int attn_grid(int nw, int batch, int heads, int nq) { return ((nq + nw * 32 - 1) / (nw * 32)) * heads * batch; }
+}  // namespace
+
+// Which forward kernel vggt_attention_fwd launches for (D, nq) under the current knobs: the
+// sibling of vggt_attention_split_plan (host arithmetic, no device call).
+extern "C" int vggt_attention_fwd_form(int D, int nq, int* form16, int* waves, int* var) {
+  const AttnForm f = attn_resolve_now(D, nq);
+  if (form16) *form16 = f.form16;
+  if (waves) *waves = f.nw;
+  if (var) *var = f.var;
+  if (D != 64 && D != 128) return VGGT_ERR_UNSUPPORTED;
+  return attn_has(f, D) ? VGGT_OK : VGGT_ERR_UNSUPPORTED;
+}
+
+// The same for vggt_attention_stamps (D = 64; *var includes the stamps bit)
+extern "C" int vggt_attention_stamps_form(int nq, int* waves, int* var) {
+  const AttnForm f = attn_resolve_stamps(g_vggt_attn_variant, g_vggt_attn_waves, g_vggt_attn_dma_half, nq);
+  if (waves) *waves = f.nw;
+  if (var) *var = f.var;
+  return attn_has(f, 64) ? VGGT_OK : VGGT_ERR_UNSUPPORTED;
+}
+
+extern "C" size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream) {
+  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !attn_resolve_now(D, nq).key_split) return 0;
+  int tail, parts, pt;
+  tail_split_of(batch, heads, nq, nk, attn_cu_count((hipStream_t)stream), &tail, &parts, &pt);
+  return (size_t)tail * parts * SPLIT_SLAB * sizeof(float);
+}
+
+// vggt_attention_fwd with a workspace: the only entry that may run the last, partial round of workgroups of the
+// 8-wave D = 64 default path split over the keys (vggt_attention_ws_bytes says how much it needs for this shape
+// under the current VGGT_TUNE_ATTN_TAIL_SPLIT; with ws == NULL it never splits).
+extern "C" int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                                     int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
+                                     int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
+                                     float scale, void* ws, size_t ws_bytes, void* stream) {
+  if (ws && (uintptr_t)ws % 16) return VGGT_ERR_ALIGN;
+  AttnArgs a;
+  const int rc = attn_args(&a, q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
+                           nq, nk, D, scale, nullptr);
+  if (rc != VGGT_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  // 16x16x32 matrix-core form: variant 161 forces it; variant 33 takes it for
-  // D = 64 when VGGT_ATTN16=1.  Off by default: faster back to back in kbench
-  // (profiles/r6c: global 1.80 vs 1.83 ms, frame 128-134 vs 135-137 us) but not
-  // in the model (r6d: global 1.87 vs 1.84 ms per launch, step 100.8 vs 100.5
-  // ms, configs[3] 1329 vs 1299 ms)
-  // VGGT_ATTN16=2: the 16x16 form only for the 4-wave (nq < 4096: frame / DINOv2) launches
-  // (never with an lse: the training recompute, vggt_attention_fwd_lse, always
-  // takes the exact-score 32x32 form whose lse the backward recomputes bit for bit)
-  const bool use16 = a.lse == nullptr && D == 64 && nw != 2 &&
-                     (g_vggt_attn_variant == 161 ||
-                      (g_vggt_attn_variant == 33 && (g_vggt_attn16 == 1 || (g_vggt_attn16 == 2 && nw == 4))));
-  if (use16) {
-    if (nw == 8) attn16_fwd_kernel<8><<<nwg, 512, 0, s>>>(a);
-    else attn16_fwd_kernel<4><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if ((g_vggt_attn_variant == 19 || g_vggt_attn_variant == 23) && D == 64 && nw != 2) {  // pipelined QK^T (3 LDS slots)
-    if (nw == 8 && g_vggt_attn_variant == 23) attn_fwd_kernel<64, 8, 23><<<nwg, 512, 0, s>>>(a);
-    else if (nw == 8) attn_fwd_kernel<64, 8, 19><<<nwg, 512, 0, s>>>(a);
-    else if (g_vggt_attn_variant == 23) attn_fwd_kernel<64, 4, 23><<<nwg, 256, 0, s>>>(a);
-    else attn_fwd_kernel<64, 4, 19><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  // Default (round 6): the 8-wave D = 64 form of variant 33 issues its LDS-DMA from the
-  // priority half only (variant 2081): global attention 1,858-1,860 -> 1,814-1,819 us,
-  // aggregator step 97.66-97.75 -> 96.56-97.21 ms, interleaved on one box
-  // (profiles/r11/ab_attn_dma_half.md).  VGGT_ATTN_DMA_HALF=0: every wave issues its piece.
-  static const bool dma_half = getenv("VGGT_ATTN_DMA_HALF") ? atoi(getenv("VGGT_ATTN_DMA_HALF")) != 0 : true;
-  if (dma_half && g_vggt_attn_variant == 33 && D == 64 && nw == 8 && !a.lse) {
-    int tail = 0, parts = 0, pt = 0;
-    if (ws) tail_split_of(batch, heads, nq, nk, attn_cu_count(s), &tail, &parts, &pt);
-    if (parts >= 2) {
-      // key-split tail: the last `tail` units as `parts` workgroups each behind the whole
-      // units, in the same launch; then the merge of their partials, on the same stream
-      if (ws_bytes < (size_t)tail * parts * SPLIT_SLAB * sizeof(float)) return VGGT_ERR_SHAPE;
-      a.n_full = nwg - tail;
-      a.parts = parts;
-      a.part_tiles = pt;
-      a.ws = (float*)ws;
-      attn_fwd_kernel<64, 8, 2081 | 8192><<<a.n_full + tail * parts, 512, 0, s>>>(a);
-      HIP_LAUNCH_CHECK();
-      attn_split_merge_kernel<<<tail * 16, 256, 0, s>>>(a, tail);
-      HIP_LAUNCH_CHECK();
-      return VGGT_OK;
-    }
-    attn_fwd_kernel<64, 8, 2081><<<nwg, 512, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (g_vggt_attn_variant == 4129 && D == 64 && nw != 2 && !a.lse) {  // 33 without the priority raise (8-wave form)
-    if (nw == 8) attn_fwd_kernel<64, 8, 4129><<<nwg, 512, 0, s>>>(a);
-    else attn_fwd_kernel<64, 4, 33><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (g_vggt_attn_variant == 2081 && D == 64 && nw != 2 && !a.lse) {  // 33, DMA by the priority half (8-wave form)
-    if (nw == 8) attn_fwd_kernel<64, 8, 2081><<<nwg, 512, 0, s>>>(a);
-    else attn_fwd_kernel<64, 4, 33><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (g_vggt_attn_variant == 545 && D == 64 && nw != 2 && !a.lse) {  // offset-free, 3 slots, DMA two tiles ahead
-    if (nw == 8) attn_fwd_kernel<64, 8, 545><<<nwg, 512, 0, s>>>(a);
-    else attn_fwd_kernel<64, 4, 545><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (g_vggt_attn_variant == 289 && D == 64 && nw != 2 && !a.lse) {  // offset-free, split-tile pipelined
-    if (nw == 8) attn_fwd_kernel<64, 8, 289><<<nwg, 512, 0, s>>>(a);
-    else attn_fwd_kernel<64, 4, 289><<<nwg, 256, 0, s>>>(a);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (g_vggt_attn_variant & 32) {  // offset-free softmax (bit 0 and the exact-score bit 64 combine)
-    const int v = (g_vggt_attn_variant & 1) + ((g_vggt_attn_variant & 64) ? 2 : 0);
-    switch ((D == 64 ? 0 : 16) + (nw == 8 ? 4 : nw == 2 ? 8 : 0) + v) {
-#define VGGT_ATTN_SCASE(DD, NWW, V)                                                               \
-  case (DD == 64 ? 0 : 16) + (NWW == 8 ? 4 : NWW == 2 ? 8 : 0) + V:                                \
-    attn_fwd_kernel<DD, NWW, 32 + (V & 1) + ((V & 2) ? 64 : 0)><<<nwg, NWW * 64, 0, s>>>(a); \
-    break;
-      VGGT_ATTN_SCASE(64, 4, 0) VGGT_ATTN_SCASE(64, 4, 1) VGGT_ATTN_SCASE(64, 4, 2) VGGT_ATTN_SCASE(64, 4, 3)
-      VGGT_ATTN_SCASE(64, 8, 0) VGGT_ATTN_SCASE(64, 8, 1) VGGT_ATTN_SCASE(64, 8, 2) VGGT_ATTN_SCASE(64, 8, 3)
-      VGGT_ATTN_SCASE(128, 4, 0) VGGT_ATTN_SCASE(128, 4, 1) VGGT_ATTN_SCASE(128, 4, 2) VGGT_ATTN_SCASE(128, 4, 3)
-      VGGT_ATTN_SCASE(128, 8, 0) VGGT_ATTN_SCASE(128, 8, 1) VGGT_ATTN_SCASE(128, 8, 2) VGGT_ATTN_SCASE(128, 8, 3)
-      VGGT_ATTN_SCASE(64, 2, 1) VGGT_ATTN_SCASE(128, 2, 1)
-#undef VGGT_ATTN_SCASE
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  switch ((D == 64 ? 0 : 32) + (nw == 8 ? 16 : 0) + (g_vggt_attn_variant & 15)) {
-#define VGGT_ATTN_CASE(DD, NWW, V) \
-  case (DD == 64 ? 0 : 32) + (NWW == 8 ? 16 : 0) + V: attn_fwd_kernel<DD, NWW, V><<<nwg, NWW * 64, 0, s>>>(a); break;
-#define VGGT_ATTN_CASES(DD, NWW)                                                                            \
-  VGGT_ATTN_CASE(DD, NWW, 0) VGGT_ATTN_CASE(DD, NWW, 1) VGGT_ATTN_CASE(DD, NWW, 2) VGGT_ATTN_CASE(DD, NWW, 3)  \
-  VGGT_ATTN_CASE(DD, NWW, 4) VGGT_ATTN_CASE(DD, NWW, 5) VGGT_ATTN_CASE(DD, NWW, 6) VGGT_ATTN_CASE(DD, NWW, 7)  \
-  VGGT_ATTN_CASE(DD, NWW, 8) VGGT_ATTN_CASE(DD, NWW, 9) VGGT_ATTN_CASE(DD, NWW, 10) VGGT_ATTN_CASE(DD, NWW, 11) \
-  VGGT_ATTN_CASE(DD, NWW, 12) VGGT_ATTN_CASE(DD, NWW, 13) VGGT_ATTN_CASE(DD, NWW, 14) VGGT_ATTN_CASE(DD, NWW, 15)
-    VGGT_ATTN_CASES(64, 4)
-    VGGT_ATTN_CASES(64, 8)
-    VGGT_ATTN_CASES(128, 4)
-    VGGT_ATTN_CASES(128, 8)
-#undef VGGT_ATTN_CASES
-#undef VGGT_ATTN_CASE
-    default: return VGGT_ERR_UNSUPPORTED;
-  }
+  AttnForm f = attn_resolve_now(D, nq);
+  const int nwg = attn_grid(f.nw, batch, heads, nq);
+  int tail = 0, parts = 0, pt = 0;
+  if (f.key_split && ws) tail_split_of(batch, heads, nq, nk, attn_cu_count(s), &tail, &parts, &pt);
+  if (parts < 2) return attn_launch(f, D, a, nwg, s);
+  // key-split tail: the last `tail` units as `parts` workgroups each behind the whole
+  // units, in the same launch; then the merge of their partials, on the same stream
+  if (ws_bytes < (size_t)tail * parts * SPLIT_SLAB * sizeof(float)) return VGGT_ERR_SHAPE;
+  a.n_full = nwg - tail;
+  a.parts = parts;
+  a.part_tiles = pt;
+  a.ws = (float*)ws;
+  f.var |= V_KEY_SPLIT;
+  const int rc2 = attn_launch(f, D, a, a.n_full + tail * parts, s);
+  if (rc2 != VGGT_OK) return rc2;
+  attn_split_merge_kernel<<<tail * 16, 256, 0, s>>>(a, tail);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
+}
+
+extern "C" int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                                  int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
+                                  int64_t ldo, int64_t o_bstride, int batch, int heads, int nq, int nk, int D,
+                                  float scale, void* stream) {
+  return vggt_attention_fwd_ws(q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch,
+                               heads, nq, nk, D, scale, nullptr, 0, stream);
+}
+
+// Diagnostic: the default forward with s_memtime segment stamps (V_STAMPS; the form: attn_resolve_stamps)
+extern "C" int vggt_attention_stamps(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
+                                     int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
+                                     int64_t ldo, int64_t o_bstride, unsigned long long* stamps, int batch, int heads,
+                                     int nq, int nk, float scale, void* stream) {
+  if (!stamps) return VGGT_ERR_SHAPE;
+  AttnArgs a;
+  const int rc = attn_args(&a, q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
+                           nq, nk, 64, scale, (float*)(void*)stamps);
+  if (rc != VGGT_OK) return rc;
+  const AttnForm f = attn_resolve_stamps(g_vggt_attn_variant, g_vggt_attn_waves, g_vggt_attn_dma_half, nq);
+  return attn_launch(f, 64, a, attn_grid(f.nw, batch, heads, nq), (hipStream_t)stream);
 }
 
 // Training recompute (alignment-head frame blocks under checkpoint, SURVEY §8f
@@ -1457,50 +1488,15 @@ static int attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride, con
 // backward's recomputed scores match bit for bit) that also stores the per-row
 // log2-sum-exp consumed by vggt_attention_bwd; its rows take their first tile's
 // max as the offset, O is normalised by the sum of the bf16-rounded p (lb_run),
-// the lse comes from the unrounded sum.
-// Diagnostic: the default forward (variant 33 -- 2081 in the 8-wave form unless
-// VGGT_ATTN_DMA_HALF=0 --, 32x32x16 form, the same 8- / 4-wave choice as
-// vggt_attention_fwd) with s_memtime segment stamps (VAR bit 1024).
-extern "C" int vggt_attention_stamps(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
-                                     int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
-                                     int64_t ldo, int64_t o_bstride, unsigned long long* stamps, int batch, int heads,
-                                     int nq, int nk, float scale, void* stream) {
-  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !stamps) return VGGT_ERR_SHAPE;
-  if ((ldq | ldk | ldv | ldo) % 8 || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16)
-    return VGGT_ERR_ALIGN;
-  if ((uint64_t)nk * (uint64_t)(ldk > ldv ? ldk : ldv) * 2 >= (1ull << 31)) return VGGT_ERR_SHAPE;
-  AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
-             q_bstride, k_bstride, v_bstride, o_bstride, batch, heads, nq, nk,
-             scale * 1.4426950408889634f, (float*)(void*)stamps};
-  const int nw = (g_vggt_attn_waves == 8 && nq >= 4096) ? 8 : 4;
-  const int nwg = ((nq + nw * 32 - 1) / (nw * 32)) * heads * batch;
-  hipStream_t s = (hipStream_t)stream;
-  static const bool dma_half = getenv("VGGT_ATTN_DMA_HALF") ? atoi(getenv("VGGT_ATTN_DMA_HALF")) != 0 : true;
-  if (nw == 8 && (g_vggt_attn_variant == 2081 || (g_vggt_attn_variant == 33 && dma_half)))
-    attn_fwd_kernel<64, 8, 2081 | 1024><<<nwg, 512, 0, s>>>(a);
-  else if (nw == 8 && g_vggt_attn_variant == 4129) attn_fwd_kernel<64, 8, 4129 | 1024><<<nwg, 512, 0, s>>>(a);
-  else if (nw == 8) attn_fwd_kernel<64, 8, 33 | 1024><<<nwg, 512, 0, s>>>(a);
-  else attn_fwd_kernel<64, 4, 33 | 1024><<<nwg, 256, 0, s>>>(a);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
-}
-
+// the lse comes from the unrounded sum.  Always the 4-wave 32x32x16 form.
 extern "C" int vggt_attention_fwd_lse(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                                       int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o,
                                       int64_t ldo, int64_t o_bstride, float* lse, int batch, int heads, int nq, int nk,
                                       int D, float scale, void* stream) {
-  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !lse) return VGGT_ERR_SHAPE;
-  if (D != 64 && D != 128) return VGGT_ERR_UNSUPPORTED;
-  if ((ldq | ldk | ldv | ldo) % 8 || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16)
-    return VGGT_ERR_ALIGN;
-  if ((uint64_t)nk * (uint64_t)(ldk > ldv ? ldk : ldv) * 2 >= (1ull << 31)) return VGGT_ERR_SHAPE;
-  AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
-             q_bstride, k_bstride, v_bstride, o_bstride, batch, heads, nq, nk,
-             scale * 1.4426950408889634f, lse};
-  const int nwg = ((nq + 127) / 128) * heads * batch;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 64) attn_fwd_kernel<64, 4, 96><<<nwg, 256, 0, s>>>(a);
-  else attn_fwd_kernel<128, 4, 96><<<nwg, 256, 0, s>>>(a);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  if (!lse) return VGGT_ERR_SHAPE;
+  AttnArgs a;
+  const int rc = attn_args(&a, q, ldq, q_bstride, k, ldk, k_bstride, v, ldv, v_bstride, o, ldo, o_bstride, batch, heads,
+                           nq, nk, D, scale, lse);
+  if (rc != VGGT_OK) return rc;
+  return attn_launch(AttnForm{false, 4, V_96, false}, D, a, attn_grid(4, batch, heads, nq), (hipStream_t)stream);
 }

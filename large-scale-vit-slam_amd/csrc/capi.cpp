@@ -6,6 +6,7 @@ extern "C" const char* vggt_version(void) { return "vggt_mi355x 0.1 gfx950"; }
 #include <stdlib.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 
 #include "tune.h"
@@ -15,11 +16,29 @@ int env_or(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
+// VGGT_TUNE_ATTN_VARIANT values (attention.hip names the bits): 3 / 7 / 11 / 15: the max-tracking kernel
+// (hoisted K reads + four-chain max, + split row sums, + MFMA row sums, + both; the other twelve combinations of
+// those four bits are retired: DESIGN.md 4.2); 19/23: pipelined QK^T; 32/33 (+64 exact scores): offset-free softmax;
+// 161 = 33 on the 16x16x32 MFMA shape (D = 64); 289 = 33 with the split-tile in-wave pipeline (D = 64);
+// 545 = 33 with 3 K|V slots, DMA two tiles ahead; 2081 = 33 with the LDS-DMA issued by the priority half of the
+// 8-wave form; 4129 = 33 without the priority raise
+// (an asynchronous ring and dynamic priorities were measured and removed: profiles/r11/ab_attn_dma_half.md)
+bool attn_variant_ok(int v) {
+  for (int ok : {3, 7, 11, 15, 19, 23, 32, 33, 96, 97, 161, 289, 545, 2081, 4129})
+    if (v == ok) return true;
+  return false;
+}
+int attn_variant_env() {
+  const int v = env_or("VGGT_ATTN_VARIANT", 33);
+  return attn_variant_ok(v) ? v : 33;  // a value vggt_tune would refuse: the default
+}
 }  // namespace
 
 int g_vggt_gemm_tile = env_or("VGGT_GEMM", -1);
 int g_vggt_attn_waves = env_or("VGGT_ATTN_WAVES", 8);  // 8-wave groups for nq >= 4096 (profiles/r2c/ab_attn_w8)
-int g_vggt_attn_variant = env_or("VGGT_ATTN_VARIANT", 33);
+int g_vggt_attn_variant = attn_variant_env();
+// env only, nonzero = on: the 8-wave D = 64 form of variant 33 issues its LDS-DMA from the priority half (runs 2081)
+int g_vggt_attn_dma_half = env_or("VGGT_ATTN_DMA_HALF", 1) != 0;
 // 2: the 16x16x32 form for the 4-wave (frame / DINOv2) launches only -- all launches measured slower in the model
 // (profiles/r6d), frame-only faster (r7b: step 98.9-99.0 -> 98.3 ms)
 int g_vggt_attn16 = env_or("VGGT_ATTN16", 2);
@@ -53,14 +72,7 @@ extern "C" int vggt_tune(int knob, int value) {
       g_vggt_attn_waves = value;
       return prev;
     case VGGT_TUNE_ATTN_VARIANT:
-      // 0-15: bit combinations of the max-tracking kernel; 19/23: pipelined QK^T;
-      // 32/33 (+64 exact scores): offset-free softmax; 161 = 33 on the 16x16x32 MFMA shape (D = 64)
-      // 289 = 33 with the split-tile in-wave pipeline (D = 64); 545 = 33 with 3 K|V slots, DMA two tiles ahead;
-      // 2081 = 33 with the LDS-DMA issued by the priority half of the 8-wave form; 4129 = 33 without the priority raise
-      // (an asynchronous ring and dynamic priorities were measured and removed: profiles/r11/ab_attn_dma_half.md)
-      if (value < 0 || (value > 15 && value != 19 && value != 23 && value != 32 && value != 33 && value != 96 &&
-                        value != 97 && value != 161 && value != 289 && value != 545 && value != 2081 && value != 4129))
-        return VGGT_ERR_UNSUPPORTED;
+      if (!attn_variant_ok(value)) return VGGT_ERR_UNSUPPORTED;
       prev = g_vggt_attn_variant;
       g_vggt_attn_variant = value;
       return prev;

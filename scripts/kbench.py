@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--only", default="gemm,norm,attn")
     ap.add_argument("--gemm-modes", default="0,1,2")
     ap.add_argument("--attn-waves", default="4,8")
-    ap.add_argument("--attn-variants", default="0")
+    ap.add_argument("--attn-variants", default="33")
     ap.add_argument("--rounds", type=int, default=1, help="repeat the attention sweep (A/B alternation)")
     ap.add_argument("--warm-s", type=float, default=3.0)
     ap.add_argument("--tokens", type=int, default=16 * 1374,

@@ -55,6 +55,8 @@ def test_tune_knobs_range_and_restore():
     assert lib.vggt_tune(6, 5) < 0  # the retired GEMM DMA-placement knob
     for knob, good, bad in ((N.TUNE_ATTN16, (0, 1, 2), (3, -1)),
                             (N.TUNE_ATTN_WAVES, (2, 4, 8), (3, 16)),
+                            (N.TUNE_ATTN_VARIANT, (3, 7, 11, 15, 19, 23, 32, 33, 96, 97, 161, 289, 545, 2081, 4129),
+                             (0, 1, 14, 16, 34, 8192, -1)),
                             (N.TUNE_LINEAR_SPLIT_K, (128, 64, 32, 16, 4096), (8, 48, 8192)),
                             (N.TUNE_LINEAR_WK, (0, 64, 128, 4096), (32, 96, 8192, -1)),
                             (N.TUNE_GEMM_BALANCE, (0, 1), (2, -1))):
