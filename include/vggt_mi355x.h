@@ -524,6 +524,47 @@ int vggt_sim3_points(const float* pts, int64_t p_bs, int B, int64_t n, const flo
 int vggt_scale_f32(float* x, int64_t bs, int B, int64_t n, const float* scale, void* stream);
 
 /*
+ * Exact batched 1-nearest-neighbour in 3-D, fp32 (PyTorch3D knn_points(K=1) as
+ * eval/reconstruction_metrics.py:48-49 and the iterative_closest_point call of
+ * eval/training_metrics.py:343-364 use it; SPEC_ASSUMPTIONS.md).  q: (B, nq_max, 3)
+ * with batch stride q_bs floats, r: (B, nr_max, 3) with r_bs; q_len / r_len:
+ * device int64[B] (clamped to [0, max]) or NULL for "all full".  For every query
+ * row below q_len: dist (B, nq_max) = the smallest distance to a reference row
+ * below r_len -- norm 2: the SQUARED Euclidean distance fma(dz,dz,fma(dy,dy,dx*dx)),
+ * norm 1: (|dx|+|dy|)+|dz|, both from coordinate differences -- and idx
+ * (B, nq_max) int64 (or NULL) its row; ties take the smallest row, a distance
+ * that does not compare below +inf (NaN coordinates, overflow, no reference
+ * rows) is never taken and a query without any gets dist = +inf, idx = -1.
+ * Rows at or past q_len get dist = 0, idx = -1.  Nothing past a length is read.
+ * split: 0 = vggt_nn1_plan's count for the device, n >= 1 = n parts of the
+ * reference range (capped at its number of 1024-point tiles); with more than
+ * one part ws (8-byte aligned, >= vggt_nn1_workspace_bytes) holds the merge
+ * keys, else ws may be NULL.  The result is bitwise independent of split and of
+ * run order.  B < 1, B > 65535 or nr_max >= 2^31: VGGT_ERR_SHAPE; norm not in
+ * {1, 2}: VGGT_ERR_UNSUPPORTED; nq_max == 0: nothing to do, VGGT_OK.
+ * vggt_nn1_plan is the policy alone (host arithmetic, no device call): the
+ * split count of the automatic mode on `cus` compute units.
+ */
+int vggt_nn1(const float* q, int64_t q_bs, const int64_t* q_len, const float* r, int64_t r_bs, const int64_t* r_len,
+             int B, int64_t nq_max, int64_t nr_max, int norm, float* dist, int64_t* idx, int split, void* ws,
+             size_t ws_bytes, void* stream);
+int vggt_nn1_plan(int B, int64_t nq_max, int64_t nr_max, int cus);
+size_t vggt_nn1_workspace_bytes(int B, int64_t nq_max, int64_t nr_max);
+
+/*
+ * The sums one rigid-ICP iteration needs, over the rows i < x_len[b] with
+ * 0 <= idx[b, i] < y_len[b] (other rows are skipped), 17 fp64 values per batch
+ * item in out (B, 17): count; sum x (3); sum y[idx] (3); sum x^T y[idx] (9,
+ * row-major, x on rows); sum |x - y[idx]|^2.  x: (B, n_max, 3), y: (B, m_max, 3)
+ * fp32, idx: (B, n_max) int64.  fp64 accumulation in a fixed order (per-workgroup
+ * partials in ws, then one pass): two runs are bitwise equal.  ws: 8-byte
+ * aligned, >= vggt_nn1_workspace_bytes(B, n_max, m_max).
+ */
+int vggt_nn1_pair_stats(const float* x, int64_t x_bs, const int64_t* x_len, const float* y, int64_t y_bs,
+                        const int64_t* y_len, const int64_t* idx, int B, int64_t n_max, int64_t m_max, double* out,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/*
  * Per-chunk pose / Sim(3) composition of FeatureAlignedVGGT.forward
  * (featureAligned_vggt.py:96-143 and the point transform of :187-196), one
  * launch, no host synchronisation:

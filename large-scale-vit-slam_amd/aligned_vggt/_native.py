@@ -113,10 +113,14 @@ _SIGS = {
     "vggt_wgrad_bias_f32": [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _i, _vp],
     "vggt_wgrad_bf16": [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _vp, ctypes.c_size_t, _vp],
     "vggt_batch_dot_f32": [_vp, _vp, _i64, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp],
+    "vggt_nn1": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
+    "vggt_nn1_plan": [_i, _i64, _i64, _i],
+    "vggt_nn1_pair_stats": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp],
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
-           "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp]}
+           "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp],
+           "vggt_nn1_workspace_bytes": [_i, _i64, _i64]}
 
 _lib = None
 
@@ -856,6 +860,84 @@ def scale_(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     rc = lib().vggt_scale_f32(_p(x), _bstride(x, n), B, n, _p(scale), _stream())
     _check(rc, "vggt_scale_f32")
     return x
+
+
+_NN_WS = {}
+
+
+def _nn_ws(device, nbytes: int) -> torch.Tensor:
+    """Grow-only per-(device, stream) scratch for vggt_nn1's merge keys and
+    vggt_nn1_pair_stats's partials (stream-ordered reuse, see _stream_key)."""
+    key = _stream_key(device)
+    table = scratch_table(_NN_WS, "nn1")
+    t = table.get(key)
+    if t is None or t.numel() * 8 < nbytes:
+        t = torch.empty((nbytes + 7) // 8 + 8, device=key[0], dtype=torch.int64)
+        table[key] = t
+    return t
+
+
+def nn1_plan(B: int, nq_max: int, nr_max: int, cus: int) -> int:
+    """vggt_nn1_plan (host arithmetic only): the automatic split count."""
+    return int(lib().vggt_nn1_plan(int(B), int(nq_max), int(nr_max), int(cus)))
+
+
+def _len_arg(lengths, B: int, device, name: str):
+    if lengths is None:
+        return None
+    t = torch.as_tensor(lengths).to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+    if t.numel() != B:
+        raise ValueError(f"{name}: {t.numel()} lengths for a batch of {B}")
+    return t
+
+
+def nn1(q: torch.Tensor, r: torch.Tensor, norm: int = 2, q_len=None, r_len=None, return_idx: bool = True,
+        split: int = 0):
+    """vggt_nn1 on the current stream: q (B, nq, 3), r (B, nr, 3) fp32 with
+    contiguous per-batch blocks -> (dist (B, nq) fp32, idx (B, nq) int64 or None)."""
+    _dev(q, "nn1")
+    _dev(r, "nn1")
+    assert q.dim() == 3 and r.dim() == 3 and q.shape[-1] == 3 and r.shape[-1] == 3 and q.shape[0] == r.shape[0], \
+        "nn1: (B, N, 3) clouds with one batch size"
+    assert q.dtype == torch.float32 and r.dtype == torch.float32, "nn1: fp32 clouds"
+    B, nq, nr = q.shape[0], q.shape[1], r.shape[1]
+    if not (nq == 0 or q[0].is_contiguous()):
+        q = q.contiguous()
+    if not (nr == 0 or r[0].is_contiguous()):
+        r = r.contiguous()
+    ql, rl = _len_arg(q_len, B, q.device, "q_len"), _len_arg(r_len, B, q.device, "r_len")
+    dist = torch.empty(B, nq, device=q.device, dtype=torch.float32)
+    idx = torch.empty(B, nq, device=q.device, dtype=torch.int64) if return_idx else None
+    L = lib()
+    nbytes = int(L.vggt_nn1_workspace_bytes(B, nq, nr))
+    ws = _nn_ws(q.device, nbytes) if nbytes else None
+    rc = L.vggt_nn1(_p(q), _bstride(q, 3 * nq), _p(ql), _p(r), _bstride(r, 3 * nr), _p(rl), B, nq, nr, int(norm),
+                    _p(dist), _p(idx), int(split), _p(ws), ws.numel() * 8 if ws is not None else 0, _stream())
+    _check(rc, "vggt_nn1")
+    return dist, idx
+
+
+def nn1_pair_stats(x: torch.Tensor, y: torch.Tensor, idx: torch.Tensor, x_len=None, y_len=None) -> torch.Tensor:
+    """vggt_nn1_pair_stats: x (B, n, 3), y (B, m, 3) fp32, idx (B, n) int64 ->
+    (B, 17) fp64 [count, sum x, sum y[idx], sum x^T y[idx] row-major, sum |x - y[idx]|^2]."""
+    _dev(x, "nn1_pair_stats")
+    _dev(y, "nn1_pair_stats")
+    _dev(idx, "nn1_pair_stats")
+    assert x.dim() == 3 and y.dim() == 3 and x.shape[-1] == 3 and y.shape[-1] == 3 and x.shape[0] == y.shape[0]
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and idx.dtype == torch.int64
+    B, n, m = x.shape[0], x.shape[1], y.shape[1]
+    assert idx.shape == (B, n)
+    x = x if n == 0 or x[0].is_contiguous() else x.contiguous()
+    y = y if m == 0 or y[0].is_contiguous() else y.contiguous()
+    idx = idx.contiguous()
+    xl, yl = _len_arg(x_len, B, x.device, "x_len"), _len_arg(y_len, B, x.device, "y_len")
+    out = torch.empty(B, 17, device=x.device, dtype=torch.float64)
+    L = lib()
+    ws = _nn_ws(x.device, max(int(L.vggt_nn1_workspace_bytes(B, max(n, 1), m)), 8))
+    rc = L.vggt_nn1_pair_stats(_p(x), _bstride(x, 3 * n), _p(xl), _p(y), _bstride(y, 3 * m), _p(yl), _p(idx), B, n, m,
+                               _p(out), _p(ws), ws.numel() * 8, _stream())
+    _check(rc, "vggt_nn1_pair_stats")
+    return out
 
 
 # ---------------------------------------------------------------- training (backward) wrappers

@@ -1,2 +1,5 @@
-"""Trajectory evaluation (eval/trajectory_metrics.py of the reference) without torchmetrics."""
+"""Evaluation (eval/trajectory_metrics.py and eval/reconstruction_metrics.py of the reference) without
+torchmetrics and pytorch3d."""
 from .trajectory_metrics import AbsoluteTrajectoryError, RelativePoseError, poses_c2w_from_predictions  # noqa: F401
+from .reconstruction_metrics import (ChamferDistanceMetrics, ICPSolution, iterative_closest_point,  # noqa: F401
+                                     nearest_neighbors)
