@@ -133,6 +133,8 @@ int vggt_gemm_bf16_gelu_pre(const void* A, int64_t lda, const void* W, int64_t l
  * (q_norm / k_norm: weights [D], eps; NULL weights = no norm) and RoPE
  * (rope_mode/pos/period/cos/sin as vggt_headnorm_rope), computed in fp32 on
  * the bf16 linear outputs and rounded once; the v block is stored as is.
+ * Every tile form gives bitwise the values of vggt_gemm_bf16 followed by
+ * vggt_qknorm_rope (the same helpers and test).
  * Replaces qkv Linear + q_norm/k_norm + rope of VGGT Attention.forward (ext
  * layers/attention.py; aggregator frame/global blocks and the alignment
  * head's frame blocks, alignment_head.py:351-366).  D in {64, 128},
@@ -152,7 +154,9 @@ int vggt_gemm_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, const 
  * N = 2*H*D: a packed kv projection (+ k_norm + RoPE on k).  Replaces the
  * q / kv Linears + vggt_headnorm_rope pair of the alignment head's temporal
  * blocks (CrossAttention, alignment_head.py:369-380): bitwise the same
- * values, one HBM pass fewer.  Shape rules as vggt_gemm_qkv.
+ * values on every tile form (one fp32 evaluation order, csrc/common.h hn_*;
+ * asserted by tests/test_gpu_gemm_edges.py), one HBM pass fewer.  Shape rules
+ * as vggt_gemm_qkv.
  */
 int vggt_gemm_headnorm(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int M, int N, int H,
                        int D, int K, void* out, int64_t ldo, const float* nw, const float* nb, float eps, int rope_mode,

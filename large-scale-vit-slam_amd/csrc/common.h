@@ -30,6 +30,67 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){lo, hi}, b16x2_t));
 }
 
+// Per-head LayerNorm + RoPE arithmetic shared by headnorm_rope_kernel (norm.hip) and the fused GEMM
+// epilogues (gemm.hip: write_tile and the persistent form), so that all of them give the same bits.
+// Left to the compiler's contraction, the copies of the same expressions rounded differently (about
+// 2 outputs per million a bf16 ulp apart, several ulps where the affine term or the rotation
+// cancels), so the fused multiply-adds are spelled out, and so is the order of the head's sums.
+__device__ __forceinline__ float hn_sq_acc(float d, float q) { return __builtin_fmaf(d, d, q); }
+__device__ __forceinline__ float hn_rstd(float q, float inv_d, float eps) { return rsqrtf(__builtin_fmaf(q, inv_d, eps)); }
+__device__ __forceinline__ float hn_affine(float x, float mean, float rstd, float w, float b) {
+  return __builtin_fmaf((x - mean) * rstd, w, b);
+}
+__device__ __forceinline__ float hn_rotate(float x, float c, float rot, float s) { return __builtin_fmaf(x, c, rot * s); }
+
+// Sum over a head whose LPH consecutive lanes hold 8 consecutive values each: MEAN = false the sum
+// of (x[j] - mean)^2, MEAN = true the sum of x[j] (mean unused).
+// 64-wide heads (LPH = 8) take the order of the persistent GEMM's epilogue, whose lane (row group
+// rg = 0..3 of the MFMA fragment layout) holds values 16 ni + 4 rg + 0..3 of the head for ni = 0..3:
+// four chains over ni, one per rg, then (chain 0 + chain 1) + (chain 2 + chain 3).  Here lane l of
+// the head holds fragment ni = l / 2, row groups 2 (l % 2) and 2 (l % 2) + 1, so a chain runs over
+// lanes l, l + 2, l + 4, l + 6 (three hops), and lanes 6 and 7 end up with the four chain sums.
+template <int LPH, bool MEAN>
+__device__ __forceinline__ float hn_head_sum(const float (&x)[8], float mean) {
+  if constexpr (LPH == 8) {
+    const int lane = threadIdx.x & 63, l = lane & 7;
+    float ca = 0.f, cb = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ia = 0.f, ib = 0.f;
+      if (k) {
+        ia = __shfl(ca, lane - 2, 64);
+        ib = __shfl(cb, lane - 2, 64);
+      }
+      float na, nb;
+      if constexpr (MEAN) {
+        na = ia + ((x[0] + x[1]) + (x[2] + x[3]));
+        nb = ib + ((x[4] + x[5]) + (x[6] + x[7]));
+      } else {
+        na = ia;
+        nb = ib;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          na = hn_sq_acc(x[j] - mean, na);
+          nb = hn_sq_acc(x[4 + j] - mean, nb);
+        }
+      }
+      if ((l >> 1) == k) {
+        ca = na;
+        cb = nb;
+      }
+    }
+    const float t = ca + cb;
+    return __shfl(t, (lane & ~7) + 6, 64) + __shfl(t, (lane & ~7) + 7, 64);
+  } else {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s = MEAN ? s + x[j] : hn_sq_acc(x[j] - mean, s);
+#pragma unroll
+    for (int o = 1; o < LPH; o <<= 1) s += __shfl_xor(s, o, 64);
+    return s;
+  }
+}
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // GELU(x) = x * Phi(x) through a branch-free erfc (Chebyshev fit, fractional

@@ -164,23 +164,10 @@ __device__ __forceinline__ void write_tile(const char* Cs, int m0, int n0, int M
       }
       const int e0 = (n % ep.hd) % D;
       if (ep.qw) {
-        float sm = 0.f;
+        const float mean = hn_head_sum<LPH, true>(x, 0.f) * (1.f / D);
+        const float rstd = hn_rstd(hn_head_sum<LPH, false>(x, mean), 1.f / D, ep.eps);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) sm += x[j];
-#pragma unroll
-        for (int o = 1; o < LPH; o <<= 1) sm += __shfl_xor(sm, o, 64);
-        const float mean = sm * (1.f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = x[j] - mean;
-          q += d * d;
-        }
-#pragma unroll
-        for (int o = 1; o < LPH; o <<= 1) q += __shfl_xor(q, o, 64);
-        const float rstd = rsqrtf(q * (1.f / D) + ep.eps);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (x[j] - mean) * rstd * nwv[j] + nbv[j];
+        for (int j = 0; j < 8; ++j) x[j] = hn_affine(x[j], mean, rstd, nwv[j], nbv[j]);
       }
       if (ep.rope_mode != VGGT_ROPE_NONE) {
         const bool two_d = ep.rope_mode == VGGT_ROPE_2D;
@@ -200,7 +187,7 @@ __device__ __forceinline__ void write_tile(const char* Cs, int m0, int n0, int M
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float partner = __shfl_xor(x[j], PL, 64);
-          y[j] = x[j] * cv[j] + (first ? -partner : partner) * sv[j];
+          y[j] = hn_rotate(x[j], cv[j], first ? -partner : partner, sv[j]);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = y[j];
@@ -1440,14 +1427,13 @@ __global__ __launch_bounds__(PNT, 1) void gemm_ppp_kernel(const bf16_t* __restri
           for (int ni = 0; ni < C::NI; ++ni)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const float d = x[ni][j] - mean;
-              q += d * d;
+              q = hn_sq_acc(x[ni][j] - mean, q);
             }
-          const float rstd = rsqrtf(rows4_sum(q) * (1.f / 64) + ep.eps);
+          const float rstd = hn_rstd(rows4_sum(q), 1.f / 64, ep.eps);
 #pragma unroll
           for (int ni = 0; ni < C::NI; ++ni)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) x[ni][j] = (x[ni][j] - mean) * rstd * lw[ni][j] + lb[ni][j];
+            for (int j = 0; j < 4; ++j) x[ni][j] = hn_affine(x[ni][j], mean, rstd, lw[ni][j], lb[ni][j]);
         }
         if (tab) {
           const int pr = (m0 + ml) % ep.period;
@@ -1460,8 +1446,11 @@ __global__ __launch_bounds__(PNT, 1) void gemm_ppp_kernel(const bf16_t* __restri
             const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 16);
             const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 16);
             const f32x4 a = x[2 * h], b = x[2 * h + 1];
-            x[2 * h] = a * c0 - b * s0;
-            x[2 * h + 1] = b * c1 + a * s1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              x[2 * h][j] = hn_rotate(a[j], c0[j], -b[j], s0[j]);
+              x[2 * h + 1][j] = hn_rotate(b[j], c1[j], a[j], s1[j]);
+            }
           }
         }
 #pragma unroll

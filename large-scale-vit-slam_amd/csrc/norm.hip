@@ -358,23 +358,10 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(const bf16_t* src, i
       }
     }
     if (w) {
-      float s = 0.f;
+      const float mean = hn_head_sum<LPH, true>(x, 0.f) * (1.f / D);
+      const float rstd = hn_rstd(hn_head_sum<LPH, false>(x, mean), 1.f / D, eps);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s += x[j];
-#pragma unroll
-      for (int o = 1; o < LPH; o <<= 1) s += __shfl_xor(s, o, 64);
-      const float mean = s * (1.f / D);
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = x[j] - mean;
-        q += d * d;
-      }
-#pragma unroll
-      for (int o = 1; o < LPH; o <<= 1) q += __shfl_xor(q, o, 64);
-      const float rstd = rsqrtf(q * (1.f / D) + eps);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = (x[j] - mean) * rstd * wv[j] + bv[j];
+      for (int j = 0; j < 8; ++j) x[j] = hn_affine(x[j], mean, rstd, wv[j], bv[j]);
     }
     if constexpr (MODE != VGGT_ROPE_NONE) {
       // rotate_half partner lives RD/2 elements away = (RD/16) lanes away
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(const bf16_t* src, i
       for (int j = 0; j < 8; ++j) {
         const float partner = __shfl_xor(x[j], PL, 64);
         const float rot = first ? -partner : partner;
-        y[j] = x[j] * cv[j] + rot * sv[j];
+        y[j] = hn_rotate(x[j], cv[j], rot, sv[j]);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = y[j];
