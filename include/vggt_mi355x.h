@@ -413,6 +413,9 @@ int vggt_cast_f32_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int ro
  * shuffle = s > 0 turns a 1x1 GEMM with co' = s*s*co columns (column
  * (dy*s+dx)*co + c) into a stride==kernel ConvTranspose2d pixel-shuffle store
  * onto the [nimg, hi*s, wi*s, co] grid.
+ * Rows must not overlap: ldx < ci on a map of more than one pixel, or ldy < co,
+ * is VGGT_ERR_SHAPE (here and in the two split-bf16 forms below, where ldy is
+ * checked only when y is given).
  */
 int vggt_conv2d_f32(const float* x, int64_t ldx, int nimg, int hi, int wi, int ci, const float* w, const float* bias,
                     int co, int kh, int kw, int stride, int pad, float* y, int64_t ldy, int relu_in, int relu_out,
@@ -476,7 +479,8 @@ int vggt_upsample_bilinear_split_sep(const float* x, int nimg, int hi, int wi, i
  * w_hi / w_lo the split packed weights of vggt_conv2d_bf16x3_pre ([>= 32 rows, 9*C], the
  * (ky, kx, ci) column order), co <= 32.  Outputs as conv2d_bf16x3_pre: y [nimg*ho*wo, ldy]
  * f32 and/or the split halves of relu?(y).  Same products and K order as the unfused
- * upsample + conv2d_bf16x3_pre.
+ * upsample + conv2d_bf16x3_pre, and the same resize arithmetic (common.h bl_*): bitwise
+ * equal to vggt_upsample_bilinear_split_sep followed by vggt_conv2d_bf16x3_pre.
  */
 int vggt_conv2d_upsample_bf16x3(const float* x, int nimg, int hi, int wi, int C, const float* pos_sep, int ho,
                                 int wo, const void* w_hi, const void* w_lo, const float* bias, int co, int relu_out,

@@ -42,6 +42,44 @@ __device__ __forceinline__ float hn_affine(float x, float mean, float rstd, floa
 }
 __device__ __forceinline__ float hn_rotate(float x, float c, float rot, float s) { return __builtin_fmaf(x, c, rot * s); }
 
+// Bilinear resize (align_corners) arithmetic shared by upsample_kernel (conv.hip) and the patch build
+// of conv_up_kernel (conv_up.hip), so that the fused resize + conv sees the very operands the unfused
+// upsample writes.  Left to the compiler's contraction, the same source expression became
+// fma(lx, v01, hx * v00) in one file and fma(hx, v00, lx * v01) in the other (an fp32 ulp apart,
+// a whole bf16 lo-half apart after the split), so the fused multiply-adds are spelled out.
+//   bl_coord: source coordinate f = s * o of output index o; i0 = (int)f, l = s * o - i0 in one
+//             rounding (may be a rounding below zero when f rounds up onto an integer), h = 1 - l
+//   bl_lerp:  hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11) + pos, evaluated as
+//             fma(hy, fma(lx, v01, hx * v00), ly * fma(lx, v11, hx * v10)), then the table add
+__device__ __forceinline__ void bl_coord(float s, int o, int& i0, float& l, float& h) {
+  const float of = (float)o;
+  const float f = s * of;
+  i0 = (int)f;
+  l = __builtin_fmaf(s, of, -(float)i0);
+  h = 1.f - l;
+}
+__device__ __forceinline__ f32x4 bl_lerp(float hy, float ly, float hx, float lx, f32x4 v00, f32x4 v01, f32x4 v10,
+                                         f32x4 v11) {
+  f32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float top = __builtin_fmaf(lx, v01[j], hx * v00[j]);
+    const float bot = __builtin_fmaf(lx, v11[j], hx * v10[j]);
+    o[j] = __builtin_fmaf(hy, top, ly * bot);
+  }
+  return o;
+}
+// split of (relu?) o into packed bf16 hi / lo: hi = bf16(o), lo = bf16(o - hi)
+__device__ __forceinline__ void bl_split(f32x4 o, uint2& ph, uint2& pl) {
+  float h[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) h[j] = round_bf(o[j]);
+  ph.x = pack_bf2(h[0], h[1]);
+  ph.y = pack_bf2(h[2], h[3]);
+  pl.x = pack_bf2(o[0] - h[0], o[1] - h[1]);
+  pl.y = pack_bf2(o[2] - h[2], o[3] - h[3]);
+}
+
 // Sum over a head whose LPH consecutive lanes hold 8 consecutive values each: MEAN = false the sum
 // of (x[j] - mean)^2, MEAN = true the sum of x[j] (mean unused).
 // 64-wide heads (LPH = 8) take the order of the persistent GEMM's epilogue, whose lane (row group

@@ -677,17 +677,18 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     const int img = (int)(p / ((int64_t)ho * wo));
     const int rem = (int)(p % ((int64_t)ho * wo));
     const int oy = rem / wo, ox = rem % wo;
-    const float fy = sh * oy, fx = sw * ox;
-    const int y0 = (int)fy, x0 = (int)fx;
+    // coordinates, lerp and split: common.h bl_* (one evaluation order with conv_up_kernel)
+    int y0, x0;
+    float ly, hy, lx, hx;
+    bl_coord(sh, oy, y0, ly, hy);
+    bl_coord(sw, ox, x0, lx, hx);
     const int y1 = min(y0 + 1, hi - 1), x1 = min(x0 + 1, wi - 1);
-    const float ly = fy - y0, lx = fx - x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
     const float* b = x + (int64_t)img * hi * wi * C;
     const f32x4 v00 = *(const f32x4*)(b + ((int64_t)y0 * wi + x0) * C + c);
     const f32x4 v01 = *(const f32x4*)(b + ((int64_t)y0 * wi + x1) * C + c);
     const f32x4 v10 = *(const f32x4*)(b + ((int64_t)y1 * wi + x0) * C + c);
     const f32x4 v11 = *(const f32x4*)(b + ((int64_t)y1 * wi + x1) * C + c);
-    f32x4 o = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    f32x4 o = bl_lerp(hy, ly, hx, lx, v00, v01, v10, v11);
     if (pos) {
       if (pos_sep) {
         const int hc = C / 2;
@@ -698,17 +699,12 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     }
     if (y) *(f32x4*)(y + p * C + c) = o;
     if (yh) {
-      float h[4];
+      if (split_relu) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (split_relu) o[j] = fmaxf(o[j], 0.f);
-        h[j] = round_bf(o[j]);
+        for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
       }
       uint2 ph, pl;
-      ph.x = pack_bf2(h[0], h[1]);
-      ph.y = pack_bf2(h[2], h[3]);
-      pl.x = pack_bf2(o[0] - h[0], o[1] - h[1]);
-      pl.y = pack_bf2(o[2] - h[2], o[3] - h[3]);
+      bl_split(o, ph, pl);
       *(uint2*)(yh + p * C + c) = ph;
       *(uint2*)(yl + p * C + c) = pl;
     }
@@ -746,6 +742,8 @@ extern "C" int vggt_conv2d_f32(const float* x, int64_t ldx, int nimg, int hi, in
   if (nimg <= 0 || hi <= 0 || wi <= 0 || ci <= 0 || co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
     return VGGT_ERR_SHAPE;
   if (ci % BK) return VGGT_ERR_SHAPE;
+  // rows must not overlap: a pixel stride below ci (on a map of more than one pixel), an output stride below co
+  if ((ldx < ci && (int64_t)nimg * hi * wi > 1) || (y && ldy < co)) return VGGT_ERR_SHAPE;
   if (shuffle && (kh != 1 || kw != 1 || stride != 1 || pad != 0 || res1 || res2 || pos)) return VGGT_ERR_UNSUPPORTED;
   if ((ldx % 4) || ((uintptr_t)x % 16) || ((uintptr_t)w % 16)) return VGGT_ERR_ALIGN;
   ConvArgs a;
@@ -776,6 +774,8 @@ static int conv_args(ConvArgs& a, const float* x, int64_t ldx, int nimg, int hi,
   if (nimg <= 0 || hi <= 0 || wi <= 0 || ci <= 0 || co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
     return VGGT_ERR_SHAPE;
   if (ci % BK) return VGGT_ERR_SHAPE;
+  // rows must not overlap: a pixel stride below ci (on a map of more than one pixel), an output stride below co
+  if ((ldx < ci && (int64_t)nimg * hi * wi > 1) || (y && ldy < co)) return VGGT_ERR_SHAPE;
   if (shuffle && (kh != 1 || kw != 1 || stride != 1 || pad != 0 || res1 || res2 || pos)) return VGGT_ERR_UNSUPPORTED;
   if ((ldx % 4) || ((uintptr_t)x % 16)) return VGGT_ERR_ALIGN;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.res1 = res1; a.res2 = res2; a.pos = pos;

@@ -135,30 +135,29 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
       uint4 hv = {0u, 0u, 0u, 0u}, lv = {0u, 0u, 0u, 0u};
       if (iy >= 0 && iy < a.ho && ix >= 0 && ix < a.wo) {
         const int c = s * CS + cc * 8;
-        const float fy = sh * iy, fx = sw * ix;
-        const int y0 = (int)fy, x0 = (int)fx;
+        int y0, x0;
+        float ly, hy, lx, hx;
+        bl_coord(sh, iy, y0, ly, hy);
+        bl_coord(sw, ix, x0, lx, hx);
         const int y1 = min(y0 + 1, a.hi - 1), x1 = min(x0 + 1, a.wi - 1);
-        const float ly = fy - y0, lx = fx - x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
         uint32_t hw[4], lw[4];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {  // two 4-channel halves, the upsample kernel's arithmetic
+        for (int h = 0; h < 2; ++h) {  // two 4-channel halves, the upsample kernel's arithmetic (common.h bl_*)
           const int ch = c + 4 * h;
           const f32x4 v00 = *(const f32x4*)(xb + ((int64_t)y0 * a.wi + x0) * C + ch);
           const f32x4 v01 = *(const f32x4*)(xb + ((int64_t)y0 * a.wi + x1) * C + ch);
           const f32x4 v10 = *(const f32x4*)(xb + ((int64_t)y1 * a.wi + x0) * C + ch);
           const f32x4 v11 = *(const f32x4*)(xb + ((int64_t)y1 * a.wi + x1) * C + ch);
-          f32x4 o = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+          f32x4 o = bl_lerp(hy, ly, hx, lx, v00, v01, v10, v11);
           if (a.pos_sep)
             o += ch < hc ? *(const f32x4*)(a.pos_sep + (int64_t)ix * hc + ch)
                          : *(const f32x4*)(a.pos_sep + (int64_t)(a.wo + iy) * hc + ch - hc);
-          float hf[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) hf[j] = round_bf(o[j]);
-          hw[2 * h] = pack_bf2(hf[0], hf[1]);
-          hw[2 * h + 1] = pack_bf2(hf[2], hf[3]);
-          lw[2 * h] = pack_bf2(o[0] - hf[0], o[1] - hf[1]);
-          lw[2 * h + 1] = pack_bf2(o[2] - hf[2], o[3] - hf[3]);
+          uint2 sph, spl;
+          bl_split(o, sph, spl);
+          hw[2 * h] = sph.x;
+          hw[2 * h + 1] = sph.y;
+          lw[2 * h] = spl.x;
+          lw[2 * h + 1] = spl.y;
         }
         hv = uint4{hw[0], hw[1], hw[2], hw[3]};
         lv = uint4{lw[0], lw[1], lw[2], lw[3]};
