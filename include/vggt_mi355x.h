@@ -634,9 +634,14 @@ int vggt_attention_bwd(const void* q, int64_t ldq, int64_t q_bstride, const void
 /*
  * Small-window attention backward (vggt_attention_small's shapes: temporal
  * cross attention, cross_attention.py:64-75, and the fp32 decoder blocks):
- * one wave per (batch, head), recomputes P; dtype for every operand.
- * dq [.., lddq] batch stride dq_bstride; dk, dv [.., lddkv] batch stride
- * dkv_bstride.  Needs (2*nq*D + 2*nk*D + 2*nq*nk)*4 <= 64 KiB.
+ * one 256-thread workgroup per (batch, head), recomputes P; dtype for every
+ * operand.  dq [.., lddq] batch stride dq_bstride; dk, dv [.., lddkv] batch
+ * stride dkv_bstride.  q, dout, k and v are staged in LDS as fp32 rows of
+ * D + 1 (one pad column), so it needs
+ * (2*nq*(D+1) + 2*nk*(D+1) + 2*nq*nk)*4 <= 64 KiB, else VGGT_ERR_SHAPE with
+ * nothing written (D = 128: nq = 29, nk = 28 fits, 29 x 29 does not; D = 64:
+ * nq = 1, nk = 125 does not).  D even; operand rows that are all 16-B aligned
+ * with D % 8 == 0 are read 16 B per lane, any other layout element by element.
  */
 int vggt_attention_small_bwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                              int64_t k_bstride, const void* v, int64_t ldv, const void* dout, int64_t ldo,
@@ -696,7 +701,10 @@ int vggt_layerscale_bwd(const float* dout, int64_t ldd, const void* branch, int 
 int vggt_gelu_fwd(const void* x, int xdtype, int64_t ldx, void* y, int ydtype, int64_t ldy, int M, int N,
                   void* stream);
 
-/* dpre = dh * GELU'(pre) (rounded to odtype); dbias += sum_m dpre (fc1 bias gradient; may be NULL). */
+/* dpre = dh * GELU'(pre) (rounded to odtype); dbias += sum_m dpre (fc1 bias gradient; may be NULL).
+ * dpre may be dh itself (same pointer, leading dimension and dtype: in place, as the MLP backward
+ * calls it) and then holds the same bits as the out-of-place call; it must not overlap pre, nor dh
+ * in any other way. */
 int vggt_gelu_bwd(const void* dh, int dhdtype, int64_t lddh, const void* pre, int predtype, int64_t ldp, void* dpre,
                   int odtype, int64_t ldo, int M, int N, float* dbias, void* ws, size_t ws_bytes, void* stream);
 

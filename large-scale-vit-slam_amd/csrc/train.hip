@@ -132,10 +132,12 @@ static void finalize_many(hipStream_t s, int nchunk, int n, int accumulate, int 
 //                    b = branch bf16, gamma = LayerScale)
 //           MODE 2: dpre = bf16(a * gelu'(b)); part0 = sum dpre
 //                   (GELU backward: a = d(hidden) bf16, b = pre-activation)
+// out may be a itself (vggt_gelu_bwd in place: each thread reads its own four
+// elements of a row before it writes them), so neither is __restrict__.
 template <int MODE>
-__global__ __launch_bounds__(256) void colred_kernel(const void* __restrict__ a, int adt, int64_t lda,
+__global__ __launch_bounds__(256) void colred_kernel(const void* a, int adt, int64_t lda,
                                                      const void* __restrict__ b, int bdt, int64_t ldb,
-                                                     const float* __restrict__ gamma, void* __restrict__ out, int odt,
+                                                     const float* __restrict__ gamma, void* out, int odt,
                                                      int64_t ldo, int M, int N, int rpc, float* __restrict__ part) {
   const int c0 = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (c0 >= N) return;
@@ -558,44 +560,81 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(
   stage(sk, k, kbs, ldk, nk);
   stage(sv, v, vbs, ldv, nk);
   __syncthreads();
-  for (int i = tid; i < nq * nk; i += 256) {
-    const int r = i / nk, c = i % nk;
-    const float* qr = sq + r * DP;
-    const float* gr = sdo + r * DP;
-    const float* kr = sk + c * DP;
-    const float* vr = sv + c * DP;
-    float s0 = 0.f, s1 = 0.f, t0 = 0.f, t1 = 0.f;
-    for (int d = 0; d < D; d += 2) {
-      s0 += qr[d] * kr[d];
-      s1 += qr[d + 1] * kr[d + 1];
-      t0 += gr[d] * vr[d];
-      t1 += gr[d + 1] * vr[d + 1];
+  // fp32 operands keep the softmax stage at one rounding per stored value: scores, dP, the row sum
+  // l and delta accumulate in fp64 (exact products), p = expf(s - m) / l, dS = p (dP - delta) formed
+  // in fp64 and rounded once.  With fp32 accumulators, the fast exponential and a reciprocal
+  // multiply, the fp32 rounding of a score entered p relatively and dP - delta cancelled: on rows
+  // with one dominant key (one query and 12 keys, the fp32 decoder's shape) dk / dv lay about twice as
+  // far from fp64 as plain fp32 arithmetic.  bf16 outputs round far above all of this and keep the
+  // fp32 accumulators and the fast forms.
+  auto scores = [&](auto zero) {
+    using acc_t = decltype(zero);
+    for (int i = tid; i < nq * nk; i += 256) {
+      const int r = i / nk, c = i % nk;
+      const float* qr = sq + r * DP;
+      const float* gr = sdo + r * DP;
+      const float* kr = sk + c * DP;
+      const float* vr = sv + c * DP;
+      acc_t s0 = zero, s1 = zero, t0 = zero, t1 = zero;
+      for (int d = 0; d < D; d += 2) {
+        s0 += (acc_t)qr[d] * (acc_t)kr[d];
+        s1 += (acc_t)qr[d + 1] * (acc_t)kr[d + 1];
+        t0 += (acc_t)gr[d] * (acc_t)vr[d];
+        t1 += (acc_t)gr[d + 1] * (acc_t)vr[d + 1];
+      }
+      sp[i] = (float)((s0 + s1) * (acc_t)scale);
+      sdp[i] = (float)(t0 + t1);
     }
-    sp[i] = (s0 + s1) * scale;
-    sdp[i] = t0 + t1;
-  }
+  };
+  if (bf)
+    scores(0.f);
+  else
+    scores(0.0);
   __syncthreads();
+  // a thread per query row; P ends in sdp's slot for dv, dS in sp's
   for (int r = tid; r < nq; r += 256) {
+    float* pr = sp + r * nk;
+    float* dr = sdp + r * nk;
     float m = -INFINITY;
-    for (int c = 0; c < nk; ++c) m = fmaxf(m, sp[r * nk + c]);
-    float l = 0.f;
-    for (int c = 0; c < nk; ++c) {
-      const float e = __expf(sp[r * nk + c] - m);
-      sp[r * nk + c] = e;
-      l += e;
-    }
-    const float inv = 1.f / l;
-    float delta = 0.f;
-    for (int c = 0; c < nk; ++c) {
-      sp[r * nk + c] *= inv;
-      delta += sp[r * nk + c] * sdp[r * nk + c];
-    }
-    // keep P in sdp's slot for dv, dS in sp's
-    for (int c = 0; c < nk; ++c) {
-      const float p = sp[r * nk + c];
-      const float ds = p * (sdp[r * nk + c] - delta);
-      sdp[r * nk + c] = p;
-      sp[r * nk + c] = ds;
+    for (int c = 0; c < nk; ++c) m = fmaxf(m, pr[c]);
+    if (bf) {
+      float l = 0.f;
+      for (int c = 0; c < nk; ++c) {
+        const float e = __expf(pr[c] - m);
+        pr[c] = e;
+        l += e;
+      }
+      const float inv = 1.f / l;
+      float delta = 0.f;
+      for (int c = 0; c < nk; ++c) {
+        pr[c] *= inv;
+        delta += pr[c] * dr[c];
+      }
+      for (int c = 0; c < nk; ++c) {
+        const float p = pr[c];
+        const float ds = p * (dr[c] - delta);
+        dr[c] = p;
+        pr[c] = ds;
+      }
+    } else {
+      double l = 0.0;
+      for (int c = 0; c < nk; ++c) {
+        const float e = expf(pr[c] - m);
+        pr[c] = e;
+        l += (double)e;
+      }
+      const float lf = (float)l;
+      double delta = 0.0;
+      for (int c = 0; c < nk; ++c) {
+        pr[c] /= lf;
+        delta += (double)pr[c] * (double)dr[c];
+      }
+      for (int c = 0; c < nk; ++c) {
+        const float p = pr[c];
+        const float ds = (float)((double)p * ((double)dr[c] - delta));
+        dr[c] = p;
+        pr[c] = ds;
+      }
     }
   }
   __syncthreads();
