@@ -164,6 +164,59 @@ int vggt_gemm_headnorm(const void* A, int64_t lda, const void* W, int64_t ldw, c
                        void* stream);
 
 /*
+ * Which kernel the four GEMM entry points above launch: host arithmetic only, no device call (without a
+ * device the device CU count is taken as 256).  The answer is the dispatcher's own (gemm_resolve in
+ * csrc/gemm.hip), under the process's current VGGT_TUNE_GEMM_TILE / VGGT_TUNE_GEMM_BALANCE and VGGT_GEMM_* /
+ * VGGT_HEADNORM_TILE environment knobs (INTEGRATION.md lists them).
+ *   entry         VGGT_GEMM_ENTRY_*; epi is read for ENTRY_BF16 only, has_out2 for GELU_PRE only (whether `pre`
+ *                 is given), N for ENTRY_BF16 / GELU_PRE / HEADNORM (QKV: 3 H D), H / D / rope_mode / period /
+ *                 tab_len for the two fused entries;
+ *   lda .. ldo2   the leading dimensions of the call (they feed the two 2^31-byte offset guards);
+ *   stream_cus    what vggt_set_stream_config gave the stream (0: unconfigured), stream_flags likewise;
+ *   force         -1; 9 / 0 ask for the first / second launch of a balance split (M = split_rows / the rest).
+ * The rule: a fixed tile mode runs its form -- 0 the 128x128 form, 1 / 2 the 256- / 128-wide ring, 3-7 the
+ * ping-pong form (3 / 7 pick the width by rounds of 256-row tiles over the device's CUs, 4 / 5 / 6 ask for
+ * 256 / 192 / 128 and fall back to the pick where N is no multiple; 192 never with D = 128 heads), 8 the
+ * two-per-CU form, 9 the persistent form -- after these fallbacks: K % 64 != 0 takes modes 0 and 3-7 (and a
+ * persistent request) to the 128-wide ring; mode 1 needs N (fused: H D) % 256 == 0, else mode 2; mode 9
+ * needs N % 256 == 0, N <= 4096, a 256-row output panel under 2^31 bytes, and for the fused entries
+ * vggt_gemm_qkv with D = 64, RoPE none / 2-D, tab_len <= 256 and its tables within 160 KiB of LDS, else it
+ * runs the 128x128 form (residual epilogue) or mode 7.  Every mode but 0 refuses (VGGT_ERR_SHAPE) a 256-row
+ * operand panel of 2^31 bytes or more.  Auto (-1) is mode 0, or mode 7 (fused, N % 256 != 0: mode 6) from
+ * M >= 4096 with K % 64 == 0 (vggt_gemm_bf16: also N % 256 == 0, N >= 2048, not the residual epilogue), and is
+ * promoted to the persistent form for GELU and fused qkv from M >= 4096, for the other bf16 / f32 GEMMs with
+ * N % 256 == 0 from M >= 16384, for the residual one from M >= 16384 with K >= 2048 -- never on a stream with
+ * VGGT_STREAM_SHORT_WORKGROUPS.  The persistent form takes 192-row tiles for the residual epilogue and where
+ * whole rounds over the stream's CUs cost 10 % less, else 256; with VGGT_TUNE_GEMM_BALANCE and a last round
+ * at most 60 % full, split_rows rows run persistent and the rest as a second launch in mode 0.
+ * Returns VGGT_OK when the library holds the kernel (the entry point would launch it), else the error the
+ * entry point returns for these shapes.
+ */
+#define VGGT_GEMM_ENTRY_BF16 0
+#define VGGT_GEMM_ENTRY_GELU_PRE 1
+#define VGGT_GEMM_ENTRY_QKV 2
+#define VGGT_GEMM_ENTRY_HEADNORM 3
+#define VGGT_GEMM_FAMILY_128 0  /* gemm_bf16_kernel, 128 x 128 tiles                  */
+#define VGGT_GEMM_FAMILY_RING 1 /* gemm_ring_kernel, 256 x bn                         */
+#define VGGT_GEMM_FAMILY_TWO 2  /* gemm_two_kernel, 256 x 128, two workgroups per CU  */
+#define VGGT_GEMM_FAMILY_PP 3   /* gemm_pp_kernel, ping-pong 256 x bn                 */
+#define VGGT_GEMM_FAMILY_PPP 4  /* gemm_ppp_kernel, persistent ping-pong bm x 256     */
+typedef struct {
+  int family;     /* VGGT_GEMM_FAMILY_* */
+  int bm, bn;     /* tile rows and columns */
+  int epi;        /* VGGT_EPI_*, or internal: 16 / 17 fused q/k norm at D = 64 / 128, 18 GELU + pre-activation */
+  int fk;         /* persistent form: 1 whole-K-tile segments, 0 half-K */
+  int grid, lds;  /* workgroups launched, dynamic LDS bytes */
+  int sched;      /* persistent form: M-tiles per tile group | split DMA << 8 */
+  int split_rows; /* balance split: rows of this (first, persistent) launch; 0 = one launch */
+  int rc;         /* VGGT_OK, or why there is nothing to launch */
+  int dev_cus;    /* the device CU count used */
+} vggt_gemm_form_t;
+int vggt_gemm_form(int entry, int epi, int has_out2, int M, int N, int K, int H, int D, int rope_mode, int period,
+                   int tab_len, int64_t lda, int64_t ldw, int64_t ldo, int64_t ldo2, int stream_cus, int stream_flags,
+                   int force, vggt_gemm_form_t* form);
+
+/*
  * Row LayerNorm over C (fp32 statistics): y = (x-mean)/sqrt(var+eps)*w + b.
  * w/b may be NULL (elementwise_affine=False).  Replaces nn.LayerNorm
  * (norm1/norm2 of every Block, alignment_head.py:203-206, DPT norm, ...).

@@ -56,6 +56,7 @@ _SIGS = {
     "vggt_attention_split_plan": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_attention_fwd_form": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_attention_stamps_form": [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    "vggt_gemm_form": [_i] * 11 + [_i64] * 4 + [_i] * 3 + [_vp],
     "vggt_patch_im2col": [_vp, _i, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _i, _vp],
     "vggt_dino_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "vggt_special_tokens": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp],
@@ -312,6 +313,35 @@ def gemm_headnorm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: tor
                                   _p(nb), float(eps), mode, _p(pos), period, _p(cos), _p(sin), tab, _stream())
     _check(rc, "vggt_gemm_headnorm")
     return out
+
+
+GEMM_ENTRY_BF16, GEMM_ENTRY_GELU_PRE, GEMM_ENTRY_QKV, GEMM_ENTRY_HEADNORM = 0, 1, 2, 3
+GEMM_FAMILY = ("128x128", "ring", "two-per-CU", "ping-pong", "persistent")
+_GEMM_FORM_FIELDS = ("family", "bm", "bn", "epi", "fk", "grid", "lds", "sched", "split_rows", "rc", "dev_cus")
+
+
+class _GemmForm(ctypes.Structure):
+    _fields_ = [(name, _i) for name in _GEMM_FORM_FIELDS]
+
+
+def gemm_form(entry: int, M: int, N: int, K: int, epi: int = EPI_BF16, has_out2: bool = False, H: int = 0, D: int = 0,
+              rope_mode: int = ROPE_NONE, period: int = 1, tab_len: int = 0, lda: Optional[int] = None,
+              ldw: Optional[int] = None, ldo: Optional[int] = None, ldo2: int = 0, stream_cus: int = 0,
+              stream_flags: int = 0, force: int = -1) -> dict:
+    """vggt_gemm_form (host arithmetic only): the kernel the GEMM entry point `entry` launches for these
+    shapes under the current knobs, as a dict of vggt_gemm_form_t's fields plus "name" (family and tile);
+    "rc" is VGGT_OK when the library holds that kernel, else the entry point's error.  Dense leading
+    dimensions unless given; stream_cus / stream_flags: what set_stream_config gave the stream."""
+    f = _GemmForm()
+    if entry == GEMM_ENTRY_QKV:
+        N = 3 * H * D
+    lib().vggt_gemm_form(entry, epi, int(has_out2), M, N, K, H, D, rope_mode, period, tab_len,
+                         K if lda is None else lda, K if ldw is None else ldw, N if ldo is None else ldo, ldo2,
+                         stream_cus, stream_flags, force, ctypes.byref(f))
+    d = {name: getattr(f, name) for name in _GEMM_FORM_FIELDS}
+    fam = GEMM_FAMILY[f.family]
+    d["name"] = fam if f.family in (0, 4) else f"{fam} {f.bm}x{f.bn}"
+    return d
 
 
 def layernorm(x: torch.Tensor, w: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float,

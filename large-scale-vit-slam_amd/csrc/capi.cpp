@@ -48,6 +48,11 @@ int g_vggt_linear_split_k = env_or("VGGT_LINEAR_SPLIT_K", 128);
 int g_vggt_linear_wk = env_or("VGGT_LINEAR_WK", 64);
 int g_vggt_gemm_balance = env_or("VGGT_GEMM_BALANCE", 0);  // whole rounds persistent + tail on 128x128: bitwise equal but
 // slower in the model (aggregator step 99.4-99.96 vs 98.7-99.0 ms, profiles/r10/ab_r10n_head_*.json), so off
+// env only (tune.h names the bits; the measurements behind each are beside its rule in gemm.hip)
+const GemmKnobs g_vggt_gemm_knobs = {env_or("VGGT_GEMM_MID", 0),   env_or("VGGT_GEMM_PERSIST", 7),
+                                     env_or("VGGT_GEMM_BM", 0),    env_or("VGGT_GEMM_FULLK", 5),
+                                     env_or("VGGT_GEMM_GM", 4) & 255, env_or("VGGT_GEMM_SPLITDMA", 1) != 0,
+                                     env_or("VGGT_HEADNORM_TILE", -1)};
 // key-split tail of the global attention launch (attention.hip, vggt_attention_fwd_ws): 0 the slot-model plan,
 // -1 off (bitwise the unsplit launch), parts | tail_blocks << 8 forced (tests, A/B).  Off by default: it is faster
 // (global attention 1,725 -> 1,679 us per launch, step -0.95 ms, profiles/r12/ab_attn_tail_split.md), but a row's

@@ -585,21 +585,6 @@ __global__ __launch_bounds__(RNT, 1) void gemm_ring_kernel(const bf16_t* __restr
   write_tile<EPI, RBM, BN, RNT, C::CROW>(Cs, m0, n0, M, ep);
 }
 
-template <int EPI, int BN>
-int launch_ring(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-                hipStream_t s) {
-  using C = RingCfg<BN>;
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, BN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              C::LDS);
-    return true;
-  }();
-  (void)attr;
-  const int nwg = ((M + RBM - 1) / RBM) * (N / BN);
-  gemm_ring_kernel<EPI, BN><<<nwg, RNT, C::LDS, s>>>(a, lda, w, ldw, M, N, K, ep);
-  return VGGT_OK;
-}
-
 // ===========================================================================
 // Two-per-CU form: 256 x 128 block tile, 4 waves (2 M x 2 N; wave tile
 // 128 x 64 = 8 x 4 fragments of v_mfma_f32_16x16x32_bf16), BK = 32, a 3-slot
@@ -772,26 +757,6 @@ __global__ __launch_bounds__(TNT, 2) void gemm_two_kernel(const bf16_t* __restri
     write_tile<EPI, TBM, TBN, TNT, C::CROW>(Cs, m0, n0, M, ep);
     __syncthreads();  // the C tile (= the ring) is read out before the next tile's DMA
   }
-}
-
-template <int EPI>
-int launch_two(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-               hipStream_t s) {
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_two_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              TwoCfg::LDS);
-    return true;
-  }();
-  (void)attr;
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  const int ntiles = ((M + TBM - 1) / TBM) * (N / TBN);
-  const int nwg = ntiles < 2 * cus ? ntiles : 2 * cus;
-  gemm_two_kernel<EPI><<<nwg, TNT, TwoCfg::LDS, s>>>(a, lda, w, ldw, M, N, K, ep);
-  return VGGT_OK;
 }
 
 // ===========================================================================
@@ -968,21 +933,6 @@ __global__ __launch_bounds__(PNT, 1) void gemm_pp_kernel(const bf16_t* __restric
   write_tile<EPI, PBM, BN, PNT, C::CROW>(Cs, m0, n0, M, ep);
 }
 
-template <int EPI, int BN>
-int launch_pp(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-              hipStream_t s) {
-  using C = PPCfg<BN>;
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, BN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              C::LDS);
-    return true;
-  }();
-  (void)attr;
-  const int nwg = ((M + PBM - 1) / PBM) * (N / BN);
-  gemm_pp_kernel<EPI, BN><<<nwg, PNT, C::LDS, s>>>(a, lda, w, ldw, M, N, K, ep);
-  return VGGT_OK;
-}
-
 // ===========================================================================
 // Persistent ping-pong form (mode 9): the 256 x 256 ping-pong main loop above,
 // one workgroup per CU looping over tiles, with the epilogue written straight
@@ -1006,18 +956,6 @@ int launch_pp(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M,
 // ===========================================================================
 constexpr int PP_MAXN = 4096;
 constexpr int PP_LDS_MAX = 160 * 1024;
-
-// VGGT_GEMM_PERSIST (A/B of the auto policy): bit 0 = the persistent form for
-// the bf16 / GELU / f32 GEMMs, bit 1 = for the fused qkv GEMM, bit 2 = for the
-// LayerScale-residual GEMMs (default all)
-inline int persist_policy(hipStream_t s) {
-  static int p = [] {
-    const char* e = getenv("VGGT_GEMM_PERSIST");
-    return e ? atoi(e) : 7;
-  }();
-  // a stream configured for short workgroups (vggt_set_stream_config) gets none of the persistent forms
-  return (vggt_stream_flags(s) & VGGT_STREAM_SHORT_WORKGROUPS) ? 0 : p;
-}
 
 // sum over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48)
 __device__ __forceinline__ float rows4_sum(float v) {
@@ -1525,120 +1463,69 @@ __global__ __launch_bounds__(PNT, 1) void gemm_ppp_kernel(const bf16_t* __restri
   }
 }
 
+// ===========================================================================
+// Dispatch.  gemm_resolve maps what a call gives (entry point, shape, leading
+// dimensions, knobs, CU counts) to a GemmForm; VGGT_GEMM_KERNELS lists every
+// kernel the library holds; gemm_launch runs a form.  vggt_gemm_form exposes
+// the resolver, and tests/test_gemm_form.py pins it to the rule-by-rule ladder
+// this code replaced.
+// ===========================================================================
+enum { G_128 = VGGT_GEMM_FAMILY_128, G_RING = VGGT_GEMM_FAMILY_RING, G_TWO = VGGT_GEMM_FAMILY_TWO,
+       G_PP = VGGT_GEMM_FAMILY_PP, G_PPP = VGGT_GEMM_FAMILY_PPP };
+typedef vggt_gemm_form_t GemmForm;
+
+// Everything the choice of a kernel reads
+struct GemmIn {
+  int entry;                                   // VGGT_GEMM_ENTRY_*
+  int epi;                                     // the public epilogue (fused entries: ignored)
+  bool out2;                                   // GELU: the pre-activation is stored too
+  int M, N, K;
+  int H, D, nreg, rope_mode, period, tab_len;  // fused entries (nreg: Epi::nreg)
+  int64_t lda, ldw, ldo, ldo2;
+  int tile, balance;                           // VGGT_TUNE_GEMM_TILE, VGGT_TUNE_GEMM_BALANCE
+  int force;                                   // -1, or the mode of one launch of a balance split: 9 first, 0 second
+  GemmKnobs knobs;
+  // CU counts.  The stream's (a CU-masked stream's share, vggt_set_stream_config; 0 = unconfigured: the
+  // device's) sizes what the persistent form does: its row tile, its one-workgroup-per-CU grid -- which
+  // would otherwise leave the masked-off CUs' share for a second, almost empty round -- and the balance
+  // split.  The device's sizes the ping-pong width picks and the two-per-CU grid, which so ignore a CU
+  // mask: kept as it was (DESIGN.md notes the width pick as a follow-up).
+  int stream_cus, dev_cus;
+  int stream_flags;                            // VGGT_STREAM_*
+};
+
 // LDS bytes of the persistent form: two K-tile buffers, the bias (and the
 // LayerScale gamma), and for the fused q/k norm + RoPE epilogue its parameters
 // and tables; 0 = does not fit
-inline int ppp_lds_bytes(int epi, int bmt, int N, const Epi& ep) {
+int ppp_lds_bytes(int epi, int bmt, int N, int rope_mode, int tab_len, int period) {
   int64_t b = 2 * ((int64_t)bmt * PBK * 2 + 256 * PBK * 2) + (int64_t)N * 4;
   if (epi == VGGT_EPI_RESID_F32) b += (int64_t)N * 4;
   if (epi == VGGT_EPI_GELU_BF16 || epi == EPI_GELU_PRE) b += (int64_t)GELU_LUT_N * 2 * 2;
   if (epi == EPI_QKNORM_D64) {
     b += 256 * 4;
-    if (ep.rope_mode == VGGT_ROPE_2D) b += 2 * (int64_t)ep.tab_len * 32 * 4 + (((int64_t)ep.period * 2 + 15) & ~15);
+    if (rope_mode == VGGT_ROPE_2D) b += 2 * (int64_t)tab_len * 32 * 4 + (((int64_t)period * 2 + 15) & ~15);
   }
   return b <= PP_LDS_MAX ? (int)b : 0;
-}
-
-inline int cu_count() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-// CUs a launch on stream s can occupy: fewer than the device's for a stream
-// created with a CU mask (vggt_set_stream_config) -- a persistent grid of
-// one workgroup per CU would otherwise leave the masked-off CUs' share for a
-// second, almost empty round
-inline int cu_count(hipStream_t s) {
-  const int n = vggt_stream_cu_count(s);
-  return n > 0 ? n : cu_count();
 }
 
 // Row tile of the persistent form: 256, or 192 when whole rounds of 192-row
 // tiles over the CUs cost at least 10% less (the N = 1024 projections at
 // M = 21,984: 344 tiles = 1.34 rounds at 256 rows, 460 = 1.80 at 192); the
-// residual epilogue always uses 192 rows (register budget: rx + acc)
-inline int ppp_pick_bm(int epi, int M, int N, hipStream_t s) {
-  if (epi == VGGT_EPI_RESID_F32) return 192;
-  static int force = [] {  // VGGT_GEMM_BM=192/256: A/B override
-    const char* e = getenv("VGGT_GEMM_BM");
-    return e ? atoi(e) : 0;
-  }();
-  if (force == 192 || force == 256) return force;
-  const int cus = cu_count(s);
+// residual epilogue always uses 192 rows (register budget: rx + acc; 128-row
+// residual tiles measured slower: proj 81.7 vs 67.4 us on the 128x128 form,
+// aggregator step 104.9 vs 101.3 ms, r3r)
+int ppp_pick_bm(bool resid, int M, int N, int force, int cus) {
+  if (resid) return 192;
+  if (force == 192 || force == 256) return force;  // VGGT_GEMM_BM=192/256: A/B override
   const long r256 = ((long)((M + 255) / 256) * (N / 256) + cus - 1) / cus;
   const long r192 = ((long)((M + 191) / 192) * (N / 256) + cus - 1) / cus;
   return r192 * 192 * 10 < r256 * 256 * 9 ? 192 : 256;
 }
 
-template <int EPI, int BMT, bool FK>
-int launch_ppp_fk(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-                  hipStream_t s) {
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_ppp_kernel<EPI, BMT, FK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              PP_LDS_MAX);
-    return true;
-  }();
-  (void)attr;
-  const int lds = ppp_lds_bytes(EPI, BMT, N, ep);
-  if (!lds) return VGGT_ERR_SHAPE;
-  const int ntiles = ((M + BMT - 1) / BMT) * (N / 256);
-  const int cus = cu_count(s);
-  const int nwg = ntiles < cus ? ntiles : cus;
-  // M-tiles per tile group (VGGT_GEMM_GM overrides; 0 = row-major).  Aggregator
-  // step 98.45 -> 97.3-97.6 ms at 4 (8: 97.55, 16: 98.5); fc1 at K = 4096 625 ->
-  // 591 us (r3y, r3z)
-  static int sched = [] {
-    const char* e = getenv("VGGT_GEMM_GM");
-    const char* d = getenv("VGGT_GEMM_SPLITDMA");
-    return (e ? atoi(e) & 255 : 4) | (d && !atoi(d) ? 0 : 256);
-  }();
-  gemm_ppp_kernel<EPI, BMT, FK><<<nwg, PNT, lds, s>>>(a, lda, w, ldw, M, N, K, ep, sched);
-  return VGGT_OK;
-}
-
-template <int EPI, int BMT>
-int launch_ppp_bm(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-                  hipStream_t s) {
-  // Whole-K-tile READ / MATH segments (VGGT_GEMM_FULLK bits: 1 bf16 / GELU / f32,
-  // 2 qkv, 4 residual; default 5).  In the model (same box, r3x kernel traces):
-  // fc2 + residual 206.6 -> 199.9 us, fc1 + GELU 196.3 -> 193.5 us.  The fused qkv
-  // form keeps the half-K segments: with both halves' fragments live its q/k-norm +
-  // RoPE epilogue spills (256 VGPRs + scratch), +2 ms per step.
-  static int fk = [] {
-    const char* e = getenv("VGGT_GEMM_FULLK");
-    return e ? atoi(e) : 5;
-  }();
-  // (GELU + pre-activation keeps half-K segments: whole-K ones spill at 256 rows)
-  const int bit = EPI == EPI_QKNORM_D64 ? 2 : EPI == VGGT_EPI_RESID_F32 ? 4 : EPI == EPI_GELU_PRE ? 8 : 1;
-  if (fk & bit) return launch_ppp_fk<EPI, BMT, true>(a, lda, w, ldw, M, N, K, ep, s);
-  return launch_ppp_fk<EPI, BMT, false>(a, lda, w, ldw, M, N, K, ep, s);
-}
-
-template <int EPI>
-int launch_ppp(const bf16_t* a, int64_t lda, const bf16_t* w, int64_t ldw, int M, int N, int K, const Epi& ep,
-               hipStream_t s) {
-  if constexpr (EPI == VGGT_EPI_RESID_F32) {
-    // (128-row residual tiles measured slower: proj 81.7 vs 67.4 us on the
-    // 128x128 form, aggregator step 104.9 vs 101.3 ms, r3r)
-    return launch_ppp_bm<EPI, 192>(a, lda, w, ldw, M, N, K, ep, s);
-  } else {
-    if (ppp_pick_bm(EPI, M, N, s) == 192) return launch_ppp_bm<EPI, 192>(a, lda, w, ldw, M, N, K, ep, s);
-    return launch_ppp_bm<EPI, 256>(a, lda, w, ldw, M, N, K, ep, s);
-  }
-}
-
 // Ping-pong tile width for an N-wide output: the BN whose whole rounds of
 // 256-row tiles over the CUs cost least (per-tile time ~ BN), larger BN on a
 // tie; 192 only where the epilogue allows it.
-inline int pp_pick_bn(int M, int N, bool allow192) {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
+int pp_pick_bn(int M, int N, bool allow192, int cus) {
   const int tm = (M + PBM - 1) / PBM;
   int best = 0;
   long best_cost = 0;
@@ -1659,34 +1546,32 @@ inline int pp_pick_bn(int M, int N, bool allow192) {
 // quantisation-aware pick.  Short M (the 154x518 sequence chunks, 6,592 rows)
 // would leave a partial last round almost empty: qkv N = 3072 at 256 wide is
 // 312 tiles = 1.22 rounds, at 192 wide 416 tiles = 1.63.
-inline int pp_auto_bn(int M, int N, bool allow192) {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
+int pp_auto_bn(int M, int N, bool allow192, int cus) {
   const long tiles256 = (long)((M + PBM - 1) / PBM) * (N / 256);
   if (N % 256 == 0 && tiles256 >= 2l * cus) return 256;
-  return pp_pick_bn(M, N, allow192);
+  return pp_pick_bn(M, N, allow192, cus);
 }
 
-}  // namespace
+// The one place that picks a kernel.  Host arithmetic on `in` alone: no HIP
+// call, no global, no environment.  The rules apply in the order written.
+GemmForm gemm_resolve(const GemmIn& in) {
+  const bool fused = in.entry == VGGT_GEMM_ENTRY_QKV || in.entry == VGGT_GEMM_ENTRY_HEADNORM;
+  const int M = in.M, N = in.N, K = in.K;
+  const GemmKnobs& kn = in.knobs;
+  const int epi = fused ? (in.D == 64 ? EPI_QKNORM_D64 : EPI_QKNORM_D128) : in.epi;
+  const bool resid = epi == VGGT_EPI_RESID_F32;
+  const bool auto_tile = in.tile < 0;  // (the knob's own value: it also holds inside the launches of a balance split)
+  // VGGT_GEMM_PERSIST (A/B of the auto policy): bit 0 = the persistent form for
+  // the bf16 / GELU / f32 GEMMs, bit 1 = for the fused qkv GEMM, bit 2 = for the
+  // LayerScale-residual GEMMs (default all); a stream configured for short workgroups
+  // (vggt_set_stream_config) gets none of the persistent forms
+  const int persist = (in.stream_flags & VGGT_STREAM_SHORT_WORKGROUPS) ? 0 : kn.persist;
+  const int cus = in.stream_cus > 0 ? in.stream_cus : in.dev_cus;  // see GemmIn
+  GemmForm f{};
+  f.epi = epi;
+  f.dev_cus = in.dev_cus;
+  f.rc = VGGT_OK;
 
-namespace {
-int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int M, int N, int K, int epi,
-              void* out, int64_t ldo, const float* gamma, float* out2, int64_t ldo2, void* stream, int force = -1) {
-  if (M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 32) return VGGT_ERR_SHAPE;
-  if ((lda % 8) || (ldw % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)bias & 15))
-    return VGGT_ERR_ALIGN;
-  if (epi == VGGT_EPI_RESID_F32 && (!gamma || ((uintptr_t)gamma & 15) || (out2 && (ldo2 % 4))))
-    return VGGT_ERR_ALIGN;
-  if (epi == VGGT_EPI_GELU_BF16 && out2 && ((ldo2 % 8) || ((uintptr_t)out2 & 15))) return VGGT_ERR_ALIGN;
-  if (epi != VGGT_EPI_RESID_F32 && epi != VGGT_EPI_GELU_BF16) out2 = nullptr;
-  if ((epi == VGGT_EPI_BF16 || epi == VGGT_EPI_GELU_BF16) ? (ldo % 8) : (ldo % 4)) return VGGT_ERR_ALIGN;
-  Epi ep{bias, out, ldo, gamma, out2, ldo2};
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t* a = (const bf16_t*)A;
-  const bf16_t* w = (const bf16_t*)W;
   // Tile choice (vggt_tune VGGT_TUNE_GEMM_TILE): 0 the 128x128 form, 1 the
   // 256x256 ring, 2 the 256x128 ring.  Auto (-1): the 256x256 ring for the MLP
   // up-projection (N >= 4096: fc1, 256 vs 278 us in the aggregator run r1i), the
@@ -1698,145 +1583,263 @@ int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const floa
   // workgroups per CU, so one's fp32 residual read-modify-write overlaps the
   // other's MFMAs) for the LayerScale+residual projections (proj 83 vs 90 us,
   // fc2 225 vs 234 us) and for small M.
-  int mode = force >= 0 ? force : g_vggt_gemm_tile;
-  if (mode < 0)
-    mode = (M >= 4096 && K % PBK == 0 && N % 256 == 0 && N >= 2048 && epi != VGGT_EPI_RESID_F32) ? 7 : 0;
-  // VGGT_GEMM_MID=1 (A/B): the 128-wide ping-pong form for the narrow (N <= 1024)
-  // LayerScale-residual / plain projections between 4,096 and 16,383 rows (the
-  // alignment head's 6,608-row proj / fc2: fc2 68.9 -> 64.0 us, gemmbench r10e)
-  static const int mid = getenv("VGGT_GEMM_MID") ? atoi(getenv("VGGT_GEMM_MID")) : 0;
-  if (g_vggt_gemm_tile < 0 && mid && mode == 0 && M >= 4096 && M < 16384 && N <= 1024 && N % 128 == 0 &&
-      K % PBK == 0 && (epi == VGGT_EPI_RESID_F32 || (mid & 2)))
-    mode = 6;
-  // auto: the persistent ping-pong form where 256x256 tiles fill several
-  // rounds of CUs (the 16x518^2 chunk: fc1 + GELU 217 -> 204 us, plain qkv
-  // shape 159 -> 139 us, scripts/gemmbench.py r3i); it falls back to mode 7
-  // for the epilogues it does not cover
-  // (GELU from M = 4,096: the 154x518 sequence chunk's fc1, 6,592 rows: 72.9 -> 64.8 us, r3w; plain bf16 stays on
-  // the one-shot forms below 16,384 rows: qkv shape 49-55 vs 55 us)
-  if (g_vggt_gemm_tile < 0 && mode == 7 && (M >= 16384 || epi == VGGT_EPI_GELU_BF16) && N <= PP_MAXN &&
-      (persist_policy(s) & 1))
-    mode = 9;
-  // ... and the narrow (N = 1024) bf16 / f32-output GEMMs of the training
-  // recompute and backward (dX = dY W): 192-row persistent tiles instead of
-  // 128x128 at 22,000 rows: K = 4096 177 -> 144 us, K = 3072 132 -> 112 us,
-  // K = 1024 51.5 -> 45.4 us (gemmbench r3tr)
-  if (g_vggt_gemm_tile < 0 && mode == 0 && epi != VGGT_EPI_RESID_F32 && M >= 16384 && N % 256 == 0 &&
-      N <= PP_MAXN && K % PBK == 0 && (persist_policy(s) & 1))
-    mode = 9;
-  // the LayerScale-residual fc2 (N = 1024, K = 4096) on 192-row persistent tiles:
-  // 216 -> 201 us, aggregator step 104.0 -> 102.3 ms (same box, r3o); the
-  // K = 1024 proj stays on the 128x128 form (76 vs 80 us)
-  if (g_vggt_gemm_tile < 0 && epi == VGGT_EPI_RESID_F32 && M >= 16384 && N % 256 == 0 && N <= PP_MAXN &&
-      K % PBK == 0 && K >= 2048 && (persist_policy(s) & 4))
-    mode = 9;
-  if (mode >= 3 && mode <= 7 && K % PBK) mode = 2;    // the ping-pong form steps K by 64
-  if (mode == 0 && K % BK) mode = 2;     // the 128x128 form steps K by 64
-  if (mode == 1 && N % 256) mode = 2;
+  int mode = in.force >= 0 ? in.force : in.tile;
+  if (fused) {
+    // vggt_gemm_headnorm only: VGGT_HEADNORM_TILE picks its form (A/B)
+    if (in.nreg == 1 && mode < 0) mode = kn.headnorm_tile;
+    // auto: the 256-wide ping-pong form on long M (fused qkv 179 vs 239 us for the
+    // 128x128 form, r1s), the 128x128 form otherwise
+    if (mode < 0) mode = (M >= 4096 && K % PBK == 0) ? (N % 256 == 0 ? 7 : 6) : 0;
+    // auto: the persistent form on the chunk shapes (D = 64 heads, RoPE-2D or none: the test below)
+    // (fused qkv of the 154x518 sequence chunk, 6,592 rows: 68.9 -> 53.6 us, r3w)
+    if (auto_tile && mode == 7 && M >= 4096 && (persist & 2)) mode = 9;
+  } else {
+    if (mode < 0)
+      mode = (M >= 4096 && K % PBK == 0 && N % 256 == 0 && N >= 2048 && !resid) ? 7 : 0;
+    // VGGT_GEMM_MID=1 (A/B): the 128-wide ping-pong form for the narrow (N <= 1024)
+    // LayerScale-residual / plain projections between 4,096 and 16,383 rows (the
+    // alignment head's 6,608-row proj / fc2: fc2 68.9 -> 64.0 us, gemmbench r10e)
+    if (auto_tile && kn.mid && mode == 0 && M >= 4096 && M < 16384 && N <= 1024 && N % 128 == 0 && K % PBK == 0 &&
+        (resid || (kn.mid & 2)))
+      mode = 6;
+    // auto: the persistent ping-pong form where 256x256 tiles fill several
+    // rounds of CUs (the 16x518^2 chunk: fc1 + GELU 217 -> 204 us, plain qkv
+    // shape 159 -> 139 us, scripts/gemmbench.py r3i); it falls back to mode 7
+    // for the epilogues it does not cover
+    // (GELU from M = 4,096: the 154x518 sequence chunk's fc1, 6,592 rows: 72.9 -> 64.8 us, r3w; plain bf16 stays on
+    // the one-shot forms below 16,384 rows: qkv shape 49-55 vs 55 us)
+    if (auto_tile && mode == 7 && (M >= 16384 || epi == VGGT_EPI_GELU_BF16) && N <= PP_MAXN && (persist & 1)) mode = 9;
+    // ... and the narrow (N = 1024) bf16 / f32-output GEMMs of the training
+    // recompute and backward (dX = dY W): 192-row persistent tiles instead of
+    // 128x128 at 22,000 rows: K = 4096 177 -> 144 us, K = 3072 132 -> 112 us,
+    // K = 1024 51.5 -> 45.4 us (gemmbench r3tr)
+    if (auto_tile && mode == 0 && !resid && M >= 16384 && N % 256 == 0 && N <= PP_MAXN && K % PBK == 0 && (persist & 1))
+      mode = 9;
+    // the LayerScale-residual fc2 (N = 1024, K = 4096) on 192-row persistent tiles:
+    // 216 -> 201 us, aggregator step 104.0 -> 102.3 ms (same box, r3o); the
+    // K = 1024 proj stays on the 128x128 form (76 vs 80 us)
+    if (auto_tile && resid && M >= 16384 && N % 256 == 0 && N <= PP_MAXN && K % PBK == 0 && K >= 2048 && (persist & 4))
+      mode = 9;
+  }
+  if (mode >= 3 && mode <= 7 && K % PBK) mode = 2;  // the ping-pong form steps K by 64
+  if (mode == 0 && K % BK) mode = 2;                // the 128x128 form steps K by 64
+  if (mode == 1 && (fused ? in.H * in.D : N) % 256) mode = 2;  // (fused: a 256-wide ring tile holds whole heads' blocks)
   // per-lane 32-bit DMA offsets span one 256-row panel
-  if (mode != 0 && (int64_t)RBM * (lda > ldw ? lda : ldw) * 2 >= (1ll << 31)) return VGGT_ERR_SHAPE;
-  if (mode == 9 && (N % 256 || N > PP_MAXN || K % PBK ||
-                    (int64_t)PBM * (ldo > ldo2 ? ldo : ldo2) * 4 >= (1ll << 31)))
-    mode = K % PBK ? 2 : epi == VGGT_EPI_RESID_F32 ? 0 : 7;  // the persistent form: N % 256 == 0, N <= 4096
+  if (mode != 0 && (int64_t)RBM * (in.lda > in.ldw ? in.lda : in.ldw) * 2 >= (1ll << 31)) {
+    f.rc = VGGT_ERR_SHAPE;
+    return f;
+  }
+  if (mode == 9) {
+    // the persistent form: N % 256 == 0, N <= 4096, 32-bit store offsets within a 256-row output panel
+    bool ok = N % 256 == 0 && N <= PP_MAXN && K % PBK == 0;
+    if (fused)
+      // ... D = 64 heads of a fused qkv row, RoPE none / 2-D with positions staged as bytes (tables of at
+      // most 256 positions) and the tables within the LDS budget.  This test keeps the launch below from
+      // ever answering "does not fit": with it, a persistent form that is resolved is launched.
+      ok = ok && in.D == 64 && in.nreg == 2 && in.rope_mode != VGGT_ROPE_1D && (int64_t)PBM * in.ldo * 2 < (1ll << 31) &&
+           ppp_lds_bytes(epi, ppp_pick_bm(false, M, N, kn.bm, cus), N, in.rope_mode, in.tab_len, in.period) > 0 &&
+           (in.rope_mode != VGGT_ROPE_2D || in.tab_len <= 256);
+    else
+      ok = ok && (int64_t)PBM * (in.ldo > in.ldo2 ? in.ldo : in.ldo2) * 4 < (1ll << 31);
+    if (!ok) mode = K % PBK ? 2 : resid ? 0 : 7;
+  }
   // Round balance (knob 10): the persistent form hands tile t to workgroup t mod CUs, so
   // 1,376 fc1 tiles (86 x 16, M = 21,984) take 6 tile-times on 256 CUs for 5.375 tiles
   // of work.  With VGGT_GEMM_BALANCE=1 the whole rounds of row panels run persistent and
   // the remaining rows on the 128x128 form (finer tiles, two per CU); rows are
   // independent and both forms accumulate K in the same order: bitwise equal.
-  if (mode == 9 && force < 0 && g_vggt_gemm_balance) {
-    const int bm = epi == VGGT_EPI_RESID_F32 ? 192 : ppp_pick_bm(epi == VGGT_EPI_GELU_BF16 && out2 ? EPI_GELU_PRE : epi, M, N, s);
-    const int tpr = N / 256, cus = cu_count(s);
+  // The form returned is the first launch's, over split_rows rows; the caller resolves
+  // the remaining rows again with force = 0.
+  int rows = M;
+  if (!fused && mode == 9 && in.force < 0 && in.balance) {
+    const int bm = ppp_pick_bm(resid, M, N, kn.bm, cus);
+    const int tpr = N / 256;
     const int64_t ntiles = (int64_t)((M + bm - 1) / bm) * tpr;
     const int64_t full = ntiles / cus, rem = ntiles % cus;
     const int m1 = (int)((full * cus / tpr) * bm);
-    if (full >= 1 && rem > 0 && rem * 10 <= (int64_t)cus * 6 && m1 > 0 && m1 < M && K % BK == 0) {
-      int rc = gemm_impl(A, lda, W, ldw, bias, m1, N, K, epi, out, ldo, gamma, out2, ldo2, stream, 9);
-      if (rc != VGGT_OK) return rc;
-      const size_t osz = (epi == VGGT_EPI_BF16 || epi == VGGT_EPI_GELU_BF16) ? 2 : 4;
-      const size_t o2sz = epi == VGGT_EPI_GELU_BF16 ? 2 : 4;
-      return gemm_impl((const bf16_t*)A + (int64_t)m1 * lda, lda, W, ldw, bias, M - m1, N, K, epi,
-                       (char*)out + (size_t)m1 * ldo * osz, ldo, gamma,
-                       out2 ? (float*)((char*)out2 + (size_t)m1 * ldo2 * o2sz) : nullptr, ldo2, stream, 0);
-    }
+    if (full >= 1 && rem > 0 && rem * 10 <= (int64_t)cus * 6 && m1 > 0 && m1 < M && K % BK == 0) rows = f.split_rows = m1;
   }
+
   if (mode == 9) {
-    int rc;
-    switch (epi) {
-      case VGGT_EPI_BF16: rc = launch_ppp<VGGT_EPI_BF16>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_GELU_BF16:
-        rc = out2 ? launch_ppp<EPI_GELU_PRE>(a, lda, w, ldw, M, N, K, ep, s)
-                  : launch_ppp<VGGT_EPI_GELU_BF16>(a, lda, w, ldw, M, N, K, ep, s);
-        break;
-      case VGGT_EPI_RESID_F32: rc = launch_ppp<VGGT_EPI_RESID_F32>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_F32: rc = launch_ppp<VGGT_EPI_F32>(a, lda, w, ldw, M, N, K, ep, s); break;
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-    if (rc != VGGT_OK) return rc;
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
+    f.family = G_PPP;
+    f.bm = ppp_pick_bm(resid, rows, N, kn.bm, cus);
+    f.bn = 256;
+    if (epi == VGGT_EPI_GELU_BF16 && in.out2) f.epi = EPI_GELU_PRE;
+    // Whole-K-tile READ / MATH segments (VGGT_GEMM_FULLK bits: 1 bf16 / GELU / f32,
+    // 2 qkv, 4 residual; default 5).  In the model (same box, r3x kernel traces):
+    // fc2 + residual 206.6 -> 199.9 us, fc1 + GELU 196.3 -> 193.5 us.  The fused qkv
+    // form keeps the half-K segments: with both halves' fragments live its q/k-norm +
+    // RoPE epilogue spills (256 VGPRs + scratch), +2 ms per step.
+    // (GELU + pre-activation keeps half-K segments: whole-K ones spill at 256 rows)
+    f.fk = (kn.fullk & (fused ? 2 : resid ? 4 : f.epi == EPI_GELU_PRE ? 8 : 1)) != 0;
+    f.lds = ppp_lds_bytes(f.epi, f.bm, N, in.rope_mode, in.tab_len, in.period);
+    if (!f.lds) f.rc = VGGT_ERR_SHAPE;
+    const int64_t ntiles = (int64_t)((rows + f.bm - 1) / f.bm) * (N / 256);
+    f.grid = (int)(ntiles < cus ? ntiles : cus);
+    // M-tiles per tile group (VGGT_GEMM_GM overrides; 0 = row-major).  Aggregator
+    // step 98.45 -> 97.3-97.6 ms at 4 (8: 97.55, 16: 98.5); fc1 at K = 4096 625 ->
+    // 591 us (r3y, r3z)
+    f.sched = kn.gm | (kn.split_dma ? 256 : 0);
+  } else if (mode == 8) {
+    f.family = G_TWO;
+    f.bm = TBM, f.bn = TBN, f.lds = TwoCfg::LDS;
+    const int ntiles = ((M + TBM - 1) / TBM) * (N / TBN);
+    f.grid = ntiles < 2 * in.dev_cus ? ntiles : 2 * in.dev_cus;
+  } else if (mode >= 3) {
+    // 192-wide tiles only with 64-wide heads (the norm's lane groups stay aligned)
+    const bool allow192 = !fused || in.D == 64;
+    int bn = mode == 4 ? 256 : mode == 5 ? 192 : mode == 6 ? 128
+             : mode == 7 ? pp_auto_bn(M, N, allow192, in.dev_cus) : pp_pick_bn(M, N, allow192, in.dev_cus);
+    if (bn == 0 || N % bn || (bn == 192 && !allow192)) bn = pp_pick_bn(M, N, allow192, in.dev_cus);
+    if (bn == 0) f.rc = VGGT_ERR_SHAPE;
+    f.family = G_PP;
+    f.bm = PBM, f.bn = bn;
+    f.lds = bn == 256 ? PPCfg<256>::LDS : bn == 192 ? PPCfg<192>::LDS : PPCfg<128>::LDS;
+    f.grid = bn ? ((M + PBM - 1) / PBM) * (N / bn) : 0;
+  } else if (mode >= 1) {
+    f.family = G_RING;
+    f.bm = RBM, f.bn = mode == 1 ? 256 : 128;
+    f.lds = mode == 1 ? RingCfg<256>::LDS : RingCfg<128>::LDS;
+    f.grid = ((M + RBM - 1) / RBM) * (N / f.bn);
+  } else {
+    f.family = G_128;
+    f.bm = BM, f.bn = BN;
+    f.grid = ((M + BM - 1) / BM) * (N / BN);
   }
-  if (mode == 8) {
-    switch (epi) {
-      case VGGT_EPI_BF16: launch_two<VGGT_EPI_BF16>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_GELU_BF16: launch_two<VGGT_EPI_GELU_BF16>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_RESID_F32: launch_two<VGGT_EPI_RESID_F32>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_F32: launch_two<VGGT_EPI_F32>(a, lda, w, ldw, M, N, K, ep, s); break;
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (mode >= 3) {
-    int bn = mode == 4 ? 256 : mode == 5 ? 192 : mode == 6 ? 128 : mode == 7 ? pp_auto_bn(M, N, true) : pp_pick_bn(M, N, true);
-    if (bn == 0 || N % bn) bn = pp_pick_bn(M, N, true);
-    if (bn == 0) return VGGT_ERR_SHAPE;
-#define VGGT_PP(E)                                                    \
-  (bn == 256   ? launch_pp<E, 256>(a, lda, w, ldw, M, N, K, ep, s)   \
-   : bn == 192 ? launch_pp<E, 192>(a, lda, w, ldw, M, N, K, ep, s)   \
-               : launch_pp<E, 128>(a, lda, w, ldw, M, N, K, ep, s))
-    switch (epi) {
-      case VGGT_EPI_BF16: VGGT_PP(VGGT_EPI_BF16); break;
-      case VGGT_EPI_GELU_BF16: VGGT_PP(VGGT_EPI_GELU_BF16); break;
-      case VGGT_EPI_RESID_F32: VGGT_PP(VGGT_EPI_RESID_F32); break;
-      case VGGT_EPI_F32: VGGT_PP(VGGT_EPI_F32); break;
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-#undef VGGT_PP
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (mode == 1) {
-    switch (epi) {
-      case VGGT_EPI_BF16: launch_ring<VGGT_EPI_BF16, 256>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_GELU_BF16: launch_ring<VGGT_EPI_GELU_BF16, 256>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_RESID_F32: launch_ring<VGGT_EPI_RESID_F32, 256>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_F32: launch_ring<VGGT_EPI_F32, 256>(a, lda, w, ldw, M, N, K, ep, s); break;
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (mode == 2) {
-    switch (epi) {
-      case VGGT_EPI_BF16: launch_ring<VGGT_EPI_BF16, 128>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_GELU_BF16: launch_ring<VGGT_EPI_GELU_BF16, 128>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_RESID_F32: launch_ring<VGGT_EPI_RESID_F32, 128>(a, lda, w, ldw, M, N, K, ep, s); break;
-      case VGGT_EPI_F32: launch_ring<VGGT_EPI_F32, 128>(a, lda, w, ldw, M, N, K, ep, s); break;
-      default: return VGGT_ERR_UNSUPPORTED;
-    }
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  const int nwg = ((M + BM - 1) / BM) * (N / BN);
-  switch (epi) {
-    case VGGT_EPI_BF16: gemm_bf16_kernel<VGGT_EPI_BF16><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep); break;
-    case VGGT_EPI_GELU_BF16: gemm_bf16_kernel<VGGT_EPI_GELU_BF16><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep); break;
-    case VGGT_EPI_RESID_F32: gemm_bf16_kernel<VGGT_EPI_RESID_F32><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep); break;
-    case VGGT_EPI_F32: gemm_bf16_kernel<VGGT_EPI_F32><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep); break;
-    default: return VGGT_ERR_UNSUPPORTED;
-  }
+  return f;
+}
+
+// Every kernel the library holds, as X(family, EPI, tile, FK): tile is BN for the
+// one-shot forms and BMT for the persistent one.  (No 192-wide ping-pong tile for
+// D = 128 heads; the residual epilogue's persistent form has 192-row tiles only.)
+#define VGGT_GEMM_K_G_128(E, T, FK) gemm_bf16_kernel<E>
+#define VGGT_GEMM_K_G_RING(E, T, FK) gemm_ring_kernel<E, T>
+#define VGGT_GEMM_K_G_TWO(E, T, FK) gemm_two_kernel<E>
+#define VGGT_GEMM_K_G_PP(E, T, FK) gemm_pp_kernel<E, T>
+#define VGGT_GEMM_K_G_PPP(E, T, FK) gemm_ppp_kernel<E, T, FK>
+// The list's order is the order the kernels stand in the code object (first the public epilogues', then the
+// fused ones'); the GELU kernels address gelu_lut relative to their own position, so moving an entry changes
+// their bytes (not their code).
+#define VGGT_GEMM_PUBLIC(X, FAM, T) \
+  X(FAM, VGGT_EPI_BF16, T, false) X(FAM, VGGT_EPI_GELU_BF16, T, false) X(FAM, VGGT_EPI_RESID_F32, T, false) X(FAM, VGGT_EPI_F32, T, false)
+#define VGGT_GEMM_FUSED(X, FAM, T) X(FAM, EPI_QKNORM_D64, T, false) X(FAM, EPI_QKNORM_D128, T, false)
+#define VGGT_GEMM_PP(X, E) X(G_PP, E, 256, false) X(G_PP, E, 192, false) X(G_PP, E, 128, false)
+#define VGGT_GEMM_PPP(X, E) X(G_PPP, E, 192, true) X(G_PPP, E, 192, false) X(G_PPP, E, 256, true) X(G_PPP, E, 256, false)
+#define VGGT_GEMM_KERNELS(X)                                                                                  \
+  VGGT_GEMM_PPP(X, VGGT_EPI_BF16) VGGT_GEMM_PPP(X, EPI_GELU_PRE) VGGT_GEMM_PPP(X, VGGT_EPI_GELU_BF16)         \
+  X(G_PPP, VGGT_EPI_RESID_F32, 192, true) X(G_PPP, VGGT_EPI_RESID_F32, 192, false) VGGT_GEMM_PPP(X, VGGT_EPI_F32) \
+  VGGT_GEMM_PUBLIC(X, G_TWO, 128)                                                                             \
+  VGGT_GEMM_PP(X, VGGT_EPI_BF16) VGGT_GEMM_PP(X, VGGT_EPI_GELU_BF16) VGGT_GEMM_PP(X, VGGT_EPI_RESID_F32)      \
+  VGGT_GEMM_PP(X, VGGT_EPI_F32)                                                                               \
+  VGGT_GEMM_PUBLIC(X, G_RING, 256) VGGT_GEMM_PUBLIC(X, G_RING, 128) VGGT_GEMM_PUBLIC(X, G_128, 128)           \
+  VGGT_GEMM_PPP(X, EPI_QKNORM_D64) VGGT_GEMM_FUSED(X, G_TWO, 128)                                             \
+  VGGT_GEMM_PP(X, EPI_QKNORM_D64) X(G_PP, EPI_QKNORM_D128, 256, false) X(G_PP, EPI_QKNORM_D128, 128, false)   \
+  VGGT_GEMM_FUSED(X, G_128, 128) VGGT_GEMM_FUSED(X, G_RING, 256) VGGT_GEMM_FUSED(X, G_RING, 128)
+
+bool gemm_is(const GemmForm& f, int family, int epi, int tile, bool fk) {
+  return f.family == family && f.epi == epi && (family == G_PPP ? f.bm : f.bn) == tile && (f.fk != 0) == fk;
+}
+
+// Whether the library holds the kernel of form `f`
+bool gemm_has(const GemmForm& f) {
+#define VGGT_GEMM_IS(FAM, E, T, FK) \
+  if (gemm_is(f, FAM, E, T, FK)) return true;
+  VGGT_GEMM_KERNELS(VGGT_GEMM_IS)
+#undef VGGT_GEMM_IS
+  return false;
+}
+
+struct GemmArgs {
+  const bf16_t* a;
+  int64_t lda;
+  const bf16_t* w;
+  int64_t ldw;
+  int M, N, K;
+  Epi ep;
+};
+
+template <int FAM, auto KERNEL>
+void gemm_start(const GemmForm& f, const GemmArgs& g, hipStream_t s) {
+  // once per kernel: the dynamic LDS it may ask for (a one-shot form's own size, the persistent form's budget)
+  static const bool attr = [&] {
+    if (FAM != G_128)
+      (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                FAM == G_PPP ? PP_LDS_MAX : f.lds);
+    return true;
+  }();
+  (void)attr;
+  constexpr int threads = FAM == G_128 ? NT : FAM == G_RING ? RNT : FAM == G_TWO ? TNT : PNT;
+  if constexpr (FAM == G_PPP) KERNEL<<<f.grid, threads, f.lds, s>>>(g.a, g.lda, g.w, g.ldw, g.M, g.N, g.K, g.ep, f.sched);
+  else KERNEL<<<f.grid, threads, f.lds, s>>>(g.a, g.lda, g.w, g.ldw, g.M, g.N, g.K, g.ep);
+}
+
+// Launches the kernel of form `f` (VGGT_ERR_UNSUPPORTED: the library does not hold it, e.g. an unknown epilogue)
+int gemm_launch(const GemmForm& f, const GemmArgs& g, hipStream_t s) {
+  if (f.rc != VGGT_OK) return f.rc;
+  if (!gemm_has(f)) return VGGT_ERR_UNSUPPORTED;
+#define VGGT_GEMM_TRY(FAM, E, T, FK) \
+  if (gemm_is(f, FAM, E, T, FK)) gemm_start<FAM, VGGT_GEMM_K_##FAM(E, T, FK)>(f, g, s);
+  VGGT_GEMM_KERNELS(VGGT_GEMM_TRY)
+#undef VGGT_GEMM_TRY
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
+}
+
+int cu_count() {
+  static int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n;
+  }();
+  return cus;
+}
+
+// The resolver's input for a call under the process's knobs (stream_cus / stream_flags: what
+// vggt_set_stream_config gave the call's stream)
+GemmIn gemm_in(int entry, int epi, bool out2, int M, int N, int K, int64_t lda, int64_t ldw, int64_t ldo, int64_t ldo2,
+               int stream_cus, int stream_flags) {
+  GemmIn in{};
+  in.entry = entry, in.epi = epi, in.out2 = out2, in.M = M, in.N = N, in.K = K;
+  in.lda = lda, in.ldw = ldw, in.ldo = ldo, in.ldo2 = ldo2;
+  in.tile = g_vggt_gemm_tile, in.balance = g_vggt_gemm_balance, in.force = -1, in.knobs = g_vggt_gemm_knobs;
+  in.stream_cus = stream_cus, in.dev_cus = cu_count(), in.stream_flags = stream_flags;
+  return in;
+}
+
+// The shape rules of the plain and of the fused entries
+bool gemm_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 32 == 0; }
+bool fused_shape_ok(int M, int H, int D, int K) {
+  return M > 0 && H > 0 && K > 0 && K % 32 == 0 && (D == 64 || D == 128) && (H * D) % 128 == 0;
+}
+
+int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int M, int N, int K, int epi,
+              void* out, int64_t ldo, const float* gamma, float* out2, int64_t ldo2, void* stream) {
+  if (!gemm_shape_ok(M, N, K)) return VGGT_ERR_SHAPE;
+  if ((lda % 8) || (ldw % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)bias & 15))
+    return VGGT_ERR_ALIGN;
+  if (epi == VGGT_EPI_RESID_F32 && (!gamma || ((uintptr_t)gamma & 15) || (out2 && (ldo2 % 4))))
+    return VGGT_ERR_ALIGN;
+  if (epi == VGGT_EPI_GELU_BF16 && out2 && ((ldo2 % 8) || ((uintptr_t)out2 & 15))) return VGGT_ERR_ALIGN;
+  if (epi != VGGT_EPI_RESID_F32 && epi != VGGT_EPI_GELU_BF16) out2 = nullptr;
+  if ((epi == VGGT_EPI_BF16 || epi == VGGT_EPI_GELU_BF16) ? (ldo % 8) : (ldo % 4)) return VGGT_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  GemmArgs g{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K, Epi{bias, out, ldo, gamma, out2, ldo2}};
+  GemmIn in = gemm_in(VGGT_GEMM_ENTRY_BF16, epi, out2 != nullptr, M, N, K, lda, ldw, ldo, ldo2,
+                      vggt_stream_cu_count(stream), vggt_stream_flags(stream));
+  const GemmForm f = gemm_resolve(in);
+  if (!f.split_rows) return gemm_launch(f, g, s);
+  // the balance split: split_rows rows persistent, then the remaining rows resolved on their own in mode 0
+  const int m1 = g.M = f.split_rows;
+  const int rc = gemm_launch(f, g, s);
+  if (rc != VGGT_OK) return rc;
+  const size_t osz = (epi == VGGT_EPI_BF16 || epi == VGGT_EPI_GELU_BF16) ? 2 : 4;
+  const size_t o2sz = epi == VGGT_EPI_GELU_BF16 ? 2 : 4;
+  g.a += (int64_t)m1 * lda;
+  g.ep.out = (char*)out + (size_t)m1 * ldo * osz;
+  if (out2) g.ep.out2 = (float*)((char*)out2 + (size_t)m1 * ldo2 * o2sz);
+  in.M = g.M = M - m1;
+  in.force = 0;
+  return gemm_launch(gemm_resolve(in), g, s);
 }
 }  // namespace
 
@@ -1860,7 +1863,7 @@ int qkv_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float
              int rope_mode, const int32_t* pos, int period, const float* cos_tab, const float* sin_tab, int tab_len,
              void* stream, int N, int nreg) {
   const int hd = H * D;
-  if (M <= 0 || H <= 0 || K <= 0 || K % 32 || (D != 64 && D != 128) || hd % 128) return VGGT_ERR_SHAPE;
+  if (!fused_shape_ok(M, H, D, K)) return VGGT_ERR_SHAPE;
   if (nreg == 2 && (qw == nullptr) != (kw == nullptr)) return VGGT_ERR_UNSUPPORTED;
   if (rope_mode != VGGT_ROPE_NONE && rope_mode != VGGT_ROPE_2D && rope_mode != VGGT_ROPE_1D) return VGGT_ERR_UNSUPPORTED;
   if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
@@ -1868,74 +1871,15 @@ int qkv_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float
   if ((lda % 8) || (ldw % 8) || (ldo % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)bias & 15) ||
       ((uintptr_t)out & 15) || (rope_mode != VGGT_ROPE_NONE && (((uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15)))
     return VGGT_ERR_ALIGN;
-  Epi ep{bias, out, ldo, nullptr, nullptr, 0, qw, qb, kw, kb, eps, hd, rope_mode, period, tab_len, pos, cos_tab,
-         sin_tab, nreg};
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t* a = (const bf16_t*)A;
-  const bf16_t* w = (const bf16_t*)W;
-  // auto: the 256-wide ping-pong form on long M (fused qkv 179 vs 239 us for the
-  // 128x128 form, r1s), the 128x128 form otherwise
-  int mode = g_vggt_gemm_tile;
-  // vggt_gemm_headnorm only: VGGT_HEADNORM_TILE picks its form (A/B)
-  static const int hn_tile = getenv("VGGT_HEADNORM_TILE") ? atoi(getenv("VGGT_HEADNORM_TILE")) : -1;
-  if (nreg == 1 && mode < 0) mode = hn_tile;
-  if (mode < 0) mode = (M >= 4096 && K % PBK == 0) ? (N % 256 == 0 ? 7 : 6) : 0;
-  if (mode >= 3 && mode <= 7 && K % PBK) mode = 2;
-  if (mode == 0 && K % BK) mode = 2;
-  if (mode == 1 && hd % 256) mode = 2;
-  if (mode != 0 && (int64_t)RBM * (lda > ldw ? lda : ldw) * 2 >= (1ll << 31)) return VGGT_ERR_SHAPE;
-  // auto: the persistent form on the chunk shapes (D = 64 heads, RoPE-2D or none)
-  // (fused qkv of the 154x518 sequence chunk, 6,592 rows: 68.9 -> 53.6 us, r3w)
-  if (g_vggt_gemm_tile < 0 && mode == 7 && M >= 4096 && (persist_policy(s) & 2)) mode = 9;
-  if (mode == 9) {
-    bool ok = D == 64 && nreg == 2 && N % 256 == 0 && N <= PP_MAXN && K % PBK == 0 && rope_mode != VGGT_ROPE_1D &&
-              (int64_t)PBM * ldo * 2 < (1ll << 31) && ppp_lds_bytes(EPI_QKNORM_D64, ppp_pick_bm(EPI_QKNORM_D64, M, N, s), N, ep) > 0;
-    if (ok && rope_mode == VGGT_ROPE_2D) {
-      // positions are staged as bytes; tables of at most 256 positions
-      ok = tab_len <= 256;
-    }
-    if (ok) {
-      launch_ppp<EPI_QKNORM_D64>(a, lda, w, ldw, M, N, K, ep, s);
-      HIP_LAUNCH_CHECK();
-      return VGGT_OK;
-    }
-    mode = K % PBK ? 2 : 7;
-  }
-  if (mode == 8) {
-    if (D == 64) launch_two<EPI_QKNORM_D64>(a, lda, w, ldw, M, N, K, ep, s);
-    else launch_two<EPI_QKNORM_D128>(a, lda, w, ldw, M, N, K, ep, s);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (mode >= 3) {
-    // 192-wide tiles only with 64-wide heads (the norm's lane groups stay aligned)
-    int bn = mode == 4 ? 256 : mode == 5 ? 192 : mode == 6 ? 128 : mode == 7 ? pp_auto_bn(M, N, D == 64) : pp_pick_bn(M, N, D == 64);
-    if (bn == 0 || N % bn || (bn == 192 && D != 64)) bn = pp_pick_bn(M, N, D == 64);
-    if (bn == 0) return VGGT_ERR_SHAPE;
-    if (D == 64) {
-      if (bn == 256) launch_pp<EPI_QKNORM_D64, 256>(a, lda, w, ldw, M, N, K, ep, s);
-      else if (bn == 192) launch_pp<EPI_QKNORM_D64, 192>(a, lda, w, ldw, M, N, K, ep, s);
-      else launch_pp<EPI_QKNORM_D64, 128>(a, lda, w, ldw, M, N, K, ep, s);
-    } else {
-      if (bn == 256) launch_pp<EPI_QKNORM_D128, 256>(a, lda, w, ldw, M, N, K, ep, s);
-      else launch_pp<EPI_QKNORM_D128, 128>(a, lda, w, ldw, M, N, K, ep, s);
-    }
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (mode == 0) {
-    const int nwg = ((M + BM - 1) / BM) * (N / BN);
-    if (D == 64) gemm_bf16_kernel<EPI_QKNORM_D64><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep);
-    else gemm_bf16_kernel<EPI_QKNORM_D128><<<nwg, NT, 0, s>>>(a, lda, w, ldw, M, N, K, ep);
-  } else if (mode == 1) {
-    if (D == 64) launch_ring<EPI_QKNORM_D64, 256>(a, lda, w, ldw, M, N, K, ep, s);
-    else launch_ring<EPI_QKNORM_D128, 256>(a, lda, w, ldw, M, N, K, ep, s);
-  } else {
-    if (D == 64) launch_ring<EPI_QKNORM_D64, 128>(a, lda, w, ldw, M, N, K, ep, s);
-    else launch_ring<EPI_QKNORM_D128, 128>(a, lda, w, ldw, M, N, K, ep, s);
-  }
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  const GemmArgs g{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K,
+                   Epi{bias, out, ldo, nullptr, nullptr, 0, qw, qb, kw, kb, eps, hd, rope_mode, period, tab_len, pos,
+                       cos_tab, sin_tab, nreg}};
+  GemmIn in = gemm_in(nreg == 2 ? VGGT_GEMM_ENTRY_QKV : VGGT_GEMM_ENTRY_HEADNORM, 0, false, M, N, K, lda, ldw, ldo, 0,
+                      vggt_stream_cu_count(stream), vggt_stream_flags(stream));
+  in.H = H, in.D = D, in.nreg = nreg, in.rope_mode = rope_mode, in.period = period, in.tab_len = tab_len;
+  // (gemm_launch's code is returned.  A persistent form whose tables do not fit would be VGGT_ERR_SHAPE, but
+  // gemm_resolve tests the LDS budget before it takes that form, so the case does not arise.)
+  return gemm_launch(gemm_resolve(in), g, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -1955,3 +1899,29 @@ extern "C" int vggt_gemm_headnorm(const void* A, int64_t lda, const void* W, int
   return qkv_impl(A, lda, W, ldw, bias, M, H, D, K, out, ldo, nw, nb, nullptr, nullptr, eps, rope_mode, pos, period,
                   cos_tab, sin_tab, tab_len, stream, N, 1);
 }
+
+// Which kernel the entries above launch (include/vggt_mi355x.h): the shape checks of the entry, then
+// gemm_resolve under the process's knobs.  No device call but the cached CU count.
+extern "C" int vggt_gemm_form(int entry, int epi, int has_out2, int M, int N, int K, int H, int D, int rope_mode,
+                              int period, int tab_len, int64_t lda, int64_t ldw, int64_t ldo, int64_t ldo2,
+                              int stream_cus, int stream_flags, int force, vggt_gemm_form_t* form) {
+  if (!form || entry < VGGT_GEMM_ENTRY_BF16 || entry > VGGT_GEMM_ENTRY_HEADNORM) return VGGT_ERR_UNSUPPORTED;
+  *form = GemmForm{};
+  const bool fused = entry >= VGGT_GEMM_ENTRY_QKV;
+  if (entry == VGGT_GEMM_ENTRY_QKV) N = 3 * H * D;
+  if (entry == VGGT_GEMM_ENTRY_HEADNORM && N != H * D && N != 2 * H * D) return form->rc = VGGT_ERR_SHAPE;
+  if (fused ? !fused_shape_ok(M, H, D, K) : !gemm_shape_ok(M, N, K)) return form->rc = VGGT_ERR_SHAPE;
+  if (fused && rope_mode != VGGT_ROPE_NONE && rope_mode != VGGT_ROPE_2D && rope_mode != VGGT_ROPE_1D)
+    return form->rc = VGGT_ERR_UNSUPPORTED;
+  if (fused && rope_mode != VGGT_ROPE_NONE && (period <= 0 || tab_len <= 0)) return form->rc = VGGT_ERR_SHAPE;
+  if (entry == VGGT_GEMM_ENTRY_GELU_PRE) epi = VGGT_EPI_GELU_BF16;
+  // (vggt_gemm_bf16 passes out2 on for the residual epilogue only, where it does not change the form)
+  GemmIn in = gemm_in(entry, epi, entry == VGGT_GEMM_ENTRY_GELU_PRE && has_out2, M, N, K, lda, ldw, ldo,
+                      fused ? 0 : ldo2, stream_cus, stream_flags);
+  in.H = H, in.D = D, in.nreg = entry == VGGT_GEMM_ENTRY_QKV ? 2 : 1, in.rope_mode = rope_mode, in.period = period;
+  in.tab_len = tab_len, in.force = force;
+  *form = gemm_resolve(in);
+  if (form->rc == VGGT_OK && !gemm_has(*form)) form->rc = VGGT_ERR_UNSUPPORTED;
+  return form->rc;
+}
+

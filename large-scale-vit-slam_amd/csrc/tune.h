@@ -11,6 +11,18 @@ extern int g_vggt_linear_one_launch; // split-K vggt_linear_f32_ws: 1 combine in
 extern int g_vggt_linear_wk;         // vggt_linear_f32_ws, M <= 256: in-workgroup split-K, ~this many k per wave (0: off)
 extern int g_vggt_gemm_balance;      // 1: persistent GEMMs with a partial last round split (whole rounds persistent, rest 128x128)
 extern int g_vggt_attn_tail_split;   // global attention key-split tail: 0 plan (auto), -1 off, parts | tail_blocks << 8 forced
+// The GEMM dispatcher's environment-only knobs (A/B switches; read once when the library loads, no vggt_tune id;
+// gemm.hip's gemm_resolve states what each one decides)
+struct GemmKnobs {
+  int mid;            // VGGT_GEMM_MID (0): bit 0 the 128-wide ping-pong form for the mid-M residual projections, bit 1 also plain ones
+  int persist;        // VGGT_GEMM_PERSIST (7): auto takes the persistent form for bit 0 bf16 / GELU / f32, bit 1 fused qkv, bit 2 residual
+  int bm;             // VGGT_GEMM_BM (0): 192 / 256 forces the persistent row tile, any other value picks by rounds
+  int fullk;          // VGGT_GEMM_FULLK (5): whole-K-tile segments for bit 0 bf16 / GELU / f32, bit 1 qkv, bit 2 residual, bit 3 GELU + pre
+  int gm;             // VGGT_GEMM_GM (4), & 255: M-tiles per tile group of the persistent form (0: row-major)
+  int split_dma;      // VGGT_GEMM_SPLITDMA (1): 0 only when set and zero
+  int headnorm_tile;  // VGGT_HEADNORM_TILE (-1): the tile mode of vggt_gemm_headnorm while VGGT_TUNE_GEMM_TILE is auto
+};
+extern const GemmKnobs g_vggt_gemm_knobs;
 // per-stream launch configuration (vggt_set_stream_config): the CUs a CU-masked
 // stream may use (0: the device's) and its VGGT_STREAM_* flags
 int vggt_stream_cu_count(void* stream);

@@ -7,8 +7,9 @@ from the bf16 inputs, computed once per shape and left unchanged.  Shapes are sm
 128 / 192 / 256-row tiles, K of one ring step (32), one K-tile (64), odd K-tile counts (192, 320)
 and K % 64 != 0 (32, 96), N that is no multiple of 256 (128, 384) or of 192.
 
-Which kernel a (tile mode, K, N) reaches (gemm_impl, M < 4096, unconfigured stream; `_reach`
-below restates it and is printed with every figure):
+Which kernel a (tile mode, K, N) reaches (M < 4096, unconfigured stream).  The label printed with
+every figure is the library's own answer (vggt_gemm_form, `_form` below), which
+tests/test_gemm_form.py pins to the dispatch rules; this table is a reading aid:
 
   mode  K % 64 == 0                                            K % 64 != 0 (32, 96)
   -1,0  128x128 (gemm_bf16_kernel)                             ring 256x128
@@ -27,7 +28,7 @@ below restates it and is printed with every figure):
         N % 256 == 0, else 128x128 for EPI_RESID_F32 and
         ping-pong 256x128 for the other epilogues
 
-The fused-epilogue GEMMs (qkv_impl) follow the same table with two differences: mode 1 takes
+The fused-epilogue GEMMs follow the same table with two differences: mode 1 takes
 the 256-wide ring when H * D % 256 == 0, and mode 9 runs persistent only for vggt_gemm_qkv with
 D = 64, N % 256 == 0, RoPE none / 2-D and a table that fits its LDS (with 192-row tiles both
 tab_len = 8 and 120 do; with 256-row tiles, which ppp_pick_bm takes on a 2-CU stream, 120 does
@@ -94,43 +95,31 @@ def N():
     return _native
 
 
-# ------------------------------------------------------------------ the dispatcher, restated for the printed figures
-def _reach(mode, epi, Nn, K):
-    """The kernel vggt_gemm_bf16 launches at M < 4096 on an unconfigured stream (gemm_impl)."""
-    mode = max(mode, 0)
-    if K % 64 and (mode == 0 or 3 <= mode <= 7):
-        mode = 2
-    if mode == 1 and Nn % 256:
-        mode = 2
-    if mode == 9 and (Nn % 256 or K % 64):
-        mode = 2 if K % 64 else 0 if epi == EPI_RESID else 7
-    if mode == 9:
-        return "persistent"
-    if mode == 8:
-        return "two-per-CU 256x128"
-    if mode >= 3:
-        bn = {4: 256, 5: 192}.get(mode, 128)
-        return f"ping-pong 256x{128 if Nn % bn else bn}"
-    return ("128x128", "ring 256x256", "ring 256x128")[mode]
+# ------------------------------------------------------------------ the dispatcher's own answers, for the printed figures
+def _native():
+    from aligned_vggt import _native as Nat
+    return Nat
 
 
-def _pick_bm(epi, M, Nn, cus):
-    """ppp_pick_bm: the persistent form's row tile on `cus` compute units."""
-    if epi == EPI_RESID:
-        return 192
-    r256 = (-(-M // 256) * (Nn // 256) + cus - 1) // cus
-    r192 = (-(-M // 192) * (Nn // 256) + cus - 1) // cus
-    return 192 if r192 * 192 * 10 < r256 * 256 * 9 else 256
+def _form(mode, M, Nn, K, epi=EPI_BF16, pre=False, cus=0, balance=0, **fused):
+    """vggt_gemm_form under tile mode `mode`: what the library launches for this call (host arithmetic,
+    no device; tests/test_gemm_form.py pins it to the dispatch rules).  fused: entry, H, D, rope_mode, tab_len."""
+    Nat = _native()
+    entry = fused.pop("entry", Nat.GEMM_ENTRY_GELU_PRE if pre else Nat.GEMM_ENTRY_BF16)
+    with _Tile(Nat, mode, balance):
+        return Nat.gemm_form(entry, M, Nn, K, epi=epi, has_out2=pre, stream_cus=cus, period=PERIOD, **fused)
 
 
-def _plan(epi, M, Nn, cus):
+def _kernel(mode, epi, M, Nn, K):
+    """The kernel vggt_gemm_bf16 launches on an unconfigured stream, by name."""
+    return _form(mode, M, Nn, K, epi)["name"]
+
+
+def _persistent_plan(epi, M, Nn, cus):
     """(row tile, tiles, whether VGGT_TUNE_GEMM_BALANCE splits the launch) of the persistent form."""
-    bm = _pick_bm(epi, M, Nn, cus)
-    tpr = Nn // 256
-    ntiles = -(-M // bm) * tpr
-    full, rem = divmod(ntiles, cus)
-    m1 = (full * cus // tpr) * bm
-    return bm, ntiles, full >= 1 and rem > 0 and rem * 10 <= cus * 6 and 0 < m1 < M
+    f = _form(9, M, Nn, 64, epi, cus=cus)
+    assert f["rc"] == 0 and f["name"] == "persistent"
+    return f["bm"], -(-M // f["bm"]) * (Nn // 256), _form(9, M, Nn, 64, epi, cus=cus, balance=1)["split_rows"] > 0
 
 
 # ------------------------------------------------------------------ bits
@@ -380,7 +369,7 @@ def test_gemm_exact(N, mode, epi):
     with _Tile(N, mode):
         for M, Nn, K in SHAPES:
             cs = _exact_case(M, Nn, K)
-            _layouts(N, epi, cs, f"exact mode {mode} [{_reach(mode, epi, Nn, K)}] {EPI_NAME[epi]} ({M},{Nn},{K})",
+            _layouts(N, epi, cs, f"exact mode {mode} [{_kernel(mode, epi, M, Nn, K)}] {EPI_NAME[epi]} ({M},{Nn},{K})",
                      _check_exact, fails)
     assert not fails, "\n".join(fails)
 
@@ -396,7 +385,7 @@ def test_gemm_interval(N, mode, epi):
     with _Tile(N, mode):
         for M, Nn, K in SHAPES:
             cs = _random_case(M, Nn, K)
-            form = _reach(mode, epi, Nn, K)
+            form = _kernel(mode, epi, M, Nn, K)
             _, nd = _layouts(N, epi, cs, f"interval mode {mode} [{form}] {EPI_NAME[epi]} ({M},{Nn},{K})",
                              _check_interval, fails)
             if nd is not None:
@@ -411,7 +400,7 @@ def test_gemm_interval(N, mode, epi):
 def test_shapes_reach_every_form():
     """The shape list drives every kernel form of the table through every epilogue it has."""
     for epi in (EPI_BF16, EPI_GELU, EPI_RESID, EPI_F32):
-        seen = {_reach(mode, epi, Nn, K) for mode in MODES for _, Nn, K in SHAPES}
+        seen = {_kernel(mode, epi, M, Nn, K) for mode in MODES for M, Nn, K in SHAPES}
         assert seen == {"128x128", "ring 256x256", "ring 256x128", "ping-pong 256x128", "ping-pong 256x192",
                         "ping-pong 256x256", "two-per-CU 256x128", "persistent"}, seen
     assert {Nn for _, Nn, _ in SHAPES} == set(N_LIST)
@@ -427,7 +416,7 @@ def test_gemm_gelu_pre(N, mode):
     with _Tile(N, mode):
         for M, Nn, K in PRE_SHAPES:
             cs = _exact_case(M, Nn, K)
-            what = f"gelu_pre mode {mode} [{_reach(mode, EPI_GELU, Nn, K)}] ({M},{Nn},{K})"
+            what = f"gelu_pre mode {mode} [{_form(mode, M, Nn, K, EPI_GELU, pre=True)['name']}] ({M},{Nn},{K})"
             (out, pre), _ = _layouts(N, EPI_GELU, cs, what, _check_exact, fails, pre=True)
             _check_same(f"{what}: pre != c", pre, cs["c"], M, Nn, fails)
             _check_same(f"{what}: pre != the EPI_BF16 launch", pre, _run(N, EPI_BF16, cs, True)[0], M, Nn, fails)
@@ -450,7 +439,7 @@ MULTI_K = [64, 128, 192]  # one, two (both buffers of the next tile prefetched) 
 
 
 def test_persistent_cases_cover_both_row_tiles_and_a_split():
-    plans = {(epi, cus, M, Nn): _plan(epi, M, Nn, cus) for epi in (EPI_BF16, EPI_RESID) for cus in (2, 3)
+    plans = {(epi, cus, M, Nn): _persistent_plan(epi, M, Nn, cus) for epi in (EPI_BF16, EPI_RESID) for cus in (2, 3)
              for M, Nn in MULTI}
     assert {p[0] for k, p in plans.items() if k[0] == EPI_BF16} == {192, 256}
     assert all(2 <= p[1] <= 12 for p in plans.values()) and any(p[1] >= 2 * k[1] for k, p in plans.items())
@@ -475,7 +464,7 @@ def test_persistent_several_tiles_per_workgroup(N, cus, mode):
                     cs = _exact_case(M, Nn, K)
                     for epi, pre in ((EPI_BF16, False), (EPI_GELU, False), (EPI_GELU, True), (EPI_RESID, False),
                                      (EPI_F32, False)):
-                        bm, ntiles, split = _plan(epi, M, Nn, cus)
+                        bm, ntiles, split = _persistent_plan(epi, M, Nn, cus)
                         res = []
                         for bal in (0, 1):
                             what = (f"persistent cus {cus} mode {mode} bal {bal} {EPI_NAME[epi]}{'+pre' if pre else ''} "
@@ -504,24 +493,11 @@ FUSED_CFG = [(0, True, 0), (0, False, 0), (1, True, 8), (1, False, 8), (2, True,
              (2, True, 120)]
 
 
-def _reach_fused(api, mode, D, hd, Nn, K, rope, tab, bm=192):
-    """qkv_impl's kernel at M < 4096 (bm: the persistent form's row tile, 192 on the whole device)."""
-    mode = max(mode, 0)
-    if K % 64 and (mode == 0 or 3 <= mode <= 7):
-        mode = 2
-    if mode == 1 and hd % 256:
-        mode = 2
-    if mode == 9:
-        lds = 2 * (bm * 128 + 256 * 128) + Nn * 4 + 1024 + (2 * tab * 128 + 16 if rope == 1 else 0)
-        if D == 64 and api == "qkv" and Nn % 256 == 0 and K % 64 == 0 and rope != 2 and lds <= 160 * 1024:
-            return "persistent"
-        mode = 2 if K % 64 else 7
-    if mode == 8:
-        return "two-per-CU 256x128"
-    if mode >= 3:
-        bn = {4: 256, 5: 192}.get(mode, 128)
-        return f"ping-pong 256x{128 if Nn % bn or (bn == 192 and D != 64) else bn}"
-    return ("128x128", "ring 256x256", "ring 256x128")[mode]
+def _kernel_fused(api, mode, D, H, M, Nn, K, rope, tab, cus=0):
+    """The kernel vggt_gemm_qkv / vggt_gemm_headnorm launches (on a stream of `cus` compute units), by name."""
+    Nat = _native()
+    return _form(mode, M, Nn, K, cus=cus, entry=Nat.GEMM_ENTRY_QKV if api == "qkv" else Nat.GEMM_ENTRY_HEADNORM,
+                 H=H, D=D, rope_mode=rope, tab_len=tab)["name"]
 
 
 def _norm_rope(x, D, w, b, eps, rope, pos):
@@ -637,8 +613,7 @@ def _fused_sweep(Nat, api, mode, D, H, fails, shapes=FUSED_SHAPES, padded_shapes
         for M, K in shapes:
             cs = _fused_case(api, D, H, cfg, M, K)
             Nn = cs["shape"][1]
-            form = _reach_fused(api, mode, D, cs["hd"], Nn, K, cfg[0], cfg[2],
-                                _pick_bm(EPI_BF16, M, Nn, cus) if cus else 192)
+            form = _kernel_fused(api, mode, D, H, M, Nn, K, cfg[0], cfg[2], cus)
             what = f"{api} mode {mode} [{form}] D {D} H {H} rope {cfg[0]} norm {int(cfg[1])} tab {cfg[2]} ({M},{Nn},{K})"
             two = _run_two_pass(Nat, cs)
             _check_fused(f"{what} two-pass", cs, two, fails)
@@ -654,7 +629,7 @@ def _fused_sweep(Nat, api, mode, D, H, fails, shapes=FUSED_SHAPES, padded_shapes
             if cus:
                 # the same call on the whole device (one tile per workgroup, 192-row tiles): rows are
                 # independent and an element's arithmetic does not depend on the tile it falls in
-                if _reach_fused(api, mode, D, cs["hd"], Nn, K, cfg[0], cfg[2]) == form:
+                if _kernel_fused(api, mode, D, H, M, Nn, K, cfg[0], cfg[2]) == form:
                     with torch.cuda.stream(torch.cuda.default_stream()), _Tile(Nat, mode):
                         _check_same(f"{what}: {cus} compute units != the whole device", got, _run_fused(Nat, cs, False),
                                     M, Nn, fails)
@@ -769,3 +744,61 @@ def test_gemm_rejections(N):
                 N.gemm_bf16(big, z(128, 64), bias[:128], out, EPI_BF16)
         torch.cuda.synchronize()
         assert (out == SENTINEL).all(), mode
+
+
+# ------------------------------------------------------------------ 7. the host-only query against the launch
+def _rc(call, *args, **kw):
+    """The entry point's return code, read back from the wrapper's exception."""
+    import re
+    try:
+        call(*args, **kw)
+        return 0
+    except RuntimeError as e:
+        return int(re.search(r"code (-?\d+)", str(e)).group(1))
+
+
+def test_query_agrees_with_launch(N):
+    """vggt_gemm_form answers VGGT_OK exactly where the entry point launches, and the entry point's
+    error code where it refuses: every (shape, tile mode, epilogue) of parts 1 / 2, the persistent
+    cases on 2 / 3 compute units with the balance split off and on, and two refusals (an operand row
+    stride of 2^31 bytes per 256 rows, an epilogue id the library does not have)."""
+    wrong, n = [], 0
+    z = lambda *s, dt=BF: torch.zeros(*s, device="cuda", dtype=dt)  # noqa: E731
+
+    def both(mode, M, Nn, K, cus, balance, a=None, epis=((EPI_BF16, False), (EPI_GELU, False), (EPI_GELU, True),
+                                                        (EPI_RESID, False), (EPI_F32, False))):
+        nonlocal n
+        a = z(M, K) if a is None else a
+        w, bias, gamma = z(Nn, K), z(Nn, dt=torch.float32), z(Nn, dt=torch.float32)
+        for epi, pre in epis:
+            out = z(M, Nn, dt=torch.float32 if epi in (EPI_RESID, EPI_F32) else BF)
+            with _Tile(N, mode, balance):
+                if pre:
+                    got = _rc(N.gemm_bf16_gelu_pre, a, w, bias, out, z(M, Nn))
+                else:
+                    got = _rc(N.gemm_bf16, a, w, bias, out, epi, gamma=gamma if epi == EPI_RESID else None)
+            want = _form(mode, M, Nn, K, epi, pre=pre, cus=cus, balance=balance, lda=a.stride(0))["rc"]
+            n += 1
+            if got != want:
+                wrong.append((mode, M, Nn, K, epi, pre, cus, balance, "launch", got, "query", want))
+
+    for mode in MODES:
+        for M, Nn, K in SHAPES:
+            both(mode, M, Nn, K, 0, 0)
+        big = torch.empty(2 * 4194304, device="cuda", dtype=BF).as_strided((2, 64), (4194304, 1))
+        both(mode, 2, 128, 64, 0, 0, a=big, epis=((EPI_BF16, False),))
+        both(mode, 129, 128, 64, 0, 0, epis=((7, False),))
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for cus in (2, 3):
+        try:
+            N.set_stream_config(side.cuda_stream, cus)
+            with torch.cuda.stream(side):
+                for (M, Nn), K, mode, balance in ((s, K, m, b) for s in MULTI for K in MULTI_K for m in (9, -1) for b in (0, 1)):
+                    both(mode, M, Nn, K, cus, balance)
+            torch.cuda.synchronize()
+        finally:
+            N.set_stream_config(side.cuda_stream, 0)
+    print(f"query against launch: {n} calls, {len(wrong)} disagree")
+    assert not wrong, wrong[:10]
+    assert n == len(MODES) * (5 * len(SHAPES) + 2) + 2 * 5 * len(MULTI) * len(MULTI_K) * 2 * 2
