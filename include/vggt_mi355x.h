@@ -217,10 +217,13 @@ int vggt_gemm_form(int entry, int epi, int has_out2, int M, int N, int K, int H,
                    int force, vggt_gemm_form_t* form);
 
 /*
- * Row LayerNorm over C (fp32 statistics): y = (x-mean)/sqrt(var+eps)*w + b.
+ * Row LayerNorm over C: y = (x-mean)/sqrt(var+eps)*w + b (two-pass statistics in fp32 for bf16
+ * outputs; in fp64, with one rounding per stored value, for fp32 outputs).
  * w/b may be NULL (elementwise_affine=False).  Replaces nn.LayerNorm
  * (norm1/norm2 of every Block, alignment_head.py:203-206, DPT norm, ...).
- * C must be a multiple of 256 and <= 4096.
+ * C must be 256 * {1, 2, 3, 4, 8, 16}; ldx, ldy multiples of 4; x, y 8-byte (bf16) or 16-byte (fp32)
+ * aligned, w and b 16-byte aligned.  y == x (same dtype, same ld: in place) is allowed; no other
+ * overlap of x and y is.  b is ignored when w is NULL.
  */
 int vggt_layernorm(const void* x, int in_dtype, int64_t ldx, const float* w, const float* b, float eps, int M, int C,
                    void* y, int out_dtype, int64_t ldy, void* stream);
@@ -264,6 +267,8 @@ int vggt_resid_add2_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy,
  * Positions: pos is int32 [period][2] (2D: y,x) or [period] (1D); row m uses
  * pos[m % period].  cos/sin tables are f32 [tab_len][rd] with rd = D/2 (2D)
  * or D (1D), layout cat(angles, angles) as in rope.py:23-44.
+ * A position outside [0, tab_len) is clamped to the first / last table row.  b is ignored when w
+ * is NULL (no normalisation at all, RoPE only).
  * Replaces Attention.q_norm/k_norm + rope (vggt attention.py, ext) and
  * CrossAttention q_norm/k_norm + rope1d (cross_attention.py:59-62).
  */
@@ -393,6 +398,8 @@ int vggt_layernorm_grouped(const void* x, int in_dtype, int64_t ldx, const float
  * Replaces the fp32 nn.Linear calls of the camera head (camera_head, ext:
  * embed_pose, poseLN_modulation, trunk Blocks, pose_branch), the alignment
  * decoder (alignment_head.py:463,475,534-538, cross blocks, gated_update.py:22-36).
+ * A, W and out may be any 4-byte aligned row-major views: 16-byte loads are used when K, lda, ldw
+ * are multiples of 4 and A and W are 16-byte aligned, scalar loads otherwise (the same sums).
  */
 int vggt_linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N, int K,
                     int act_in, int epi, float* out, int64_t ldo, const float* gamma, void* stream);
@@ -448,7 +455,8 @@ int vggt_attention_small(const void* q, int64_t ldq, int64_t q_bstride, const vo
                          const void* v, int64_t ldv, void* o, int64_t ldo, int64_t o_bstride, int dtype, int batch,
                          int heads, int nq, int nk, int D, float scale, void* stream);
 
-/* fp32 variant of vggt_headnorm_rope (decoder / camera head run in fp32). */
+/* fp32 variant of vggt_headnorm_rope (decoder / camera head run in fp32): D a multiple of 4 up to
+ * 1024, any col_off (scalar loads); positions clamped and b ignored without w as there. */
 int vggt_headnorm_rope_f32(float* buf, int64_t ld, int col_off, int M, int H, int D, const float* w, const float* b,
                            float eps, int rope_mode, const int32_t* pos, int period, const float* cos_tab,
                            const float* sin_tab, int tab_len, void* stream);

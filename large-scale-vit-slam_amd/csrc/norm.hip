@@ -9,15 +9,27 @@ namespace {
 // NV = C / 256 float4 per lane (C = 256 * NV).
 // Row r of the logical [M, C] input maps to group g = r / G, i = r % G:
 //   x row = g*xgs + xoff + i,  y row = g*ygs + yoff + i   (identity: G = M).
+// x and y carry no __restrict__: the model normalises in place (y == x with equal
+// dtypes and strides; a wave reads its whole row before it stores any of it).
+// fp32 outputs (the fp32 heads: a few hundred rows) take their statistics and the
+// affine step in fp64 with one rounding per stored value: in fp32, 4 NV serial additions
+// per lane and rsqrtf left a row up to 5 x as far from fp64 as a plain fp32 evaluation
+// (C = 4096, mean 1000: 3.3e-7 against 6.4e-8 of the row norm), which only a bf16
+// rounding hides.  bf16 outputs keep the fp32 statistics (and their bits).
 struct RowMap {
   int G, xgs, xoff, ygs, yoff;
 };
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 template <int NV, bool IN_BF16, bool OUT_BF16>
-__global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ x, int64_t ldx,
-                                                        const float* __restrict__ w, const float* __restrict__ b,
-                                                        float eps, int M, void* __restrict__ y, int64_t ldy,
-                                                        RowMap rm) {
+__global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t ldx, const float* __restrict__ w,
+                                                        const float* __restrict__ b, float eps, int M, void* y,
+                                                        int64_t ldy, RowMap rm) {
   constexpr int C = NV * 256;
   const int lane = threadIdx.x & 63;
   const int lrow = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -40,6 +52,39 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[i][j] = u[j];
     }
+  }
+  if constexpr (!OUT_BF16) {
+    double sd = 0.;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sd += (double)v[i][j];
+    const double mean = wave_sum_f64(sd) / C;  // a quotient: the mean of a constant row is exact for every C
+    double qd = 0.;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double d = (double)v[i][j] - mean;
+        qd = fma(d, d, qd);
+      }
+    const double rstd = 1.0 / sqrt(wave_sum_f64(qd) / C + (double)eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = i * 256 + lane * 4;
+      f32x4 o;
+      if (w) {
+        const f32x4 wv = *(const f32x4*)(w + c);
+        const f32x4 bv = b ? *(const f32x4*)(b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (float)(((double)v[i][j] - mean) * rstd * (double)wv[j] + (double)bv[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (float)(((double)v[i][j] - mean) * rstd);
+      }
+      *(f32x4*)((float*)y + orow * ldy + c) = o;
+    }
+    return;
   }
   float s = 0.f;
 #pragma unroll
@@ -437,6 +482,7 @@ extern "C" int vggt_layernorm_grouped(const void* x, int in_dtype, int64_t ldx, 
   if ((ldx % 4) || (ldy % 4) || ((uintptr_t)x % 8) || ((uintptr_t)y % 8)) return VGGT_ERR_ALIGN;
   if (!in_dtype && ((uintptr_t)x % 16)) return VGGT_ERR_ALIGN;
   if (!out_dtype && ((uintptr_t)y % 16)) return VGGT_ERR_ALIGN;
+  if ((w && ((uintptr_t)w % 16)) || (b && ((uintptr_t)b % 16))) return VGGT_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int ib = in_dtype == VGGT_DTYPE_BF16, ob = out_dtype == VGGT_DTYPE_BF16;
   switch (C / 256) {
