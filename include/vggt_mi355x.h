@@ -81,12 +81,18 @@ const char* vggt_version(void);
 #define VGGT_TUNE_GEMM_BALANCE 10 /* vggt_gemm_bf16 on the persistent form: 1 the whole rounds of row panels
                                      persistent and the remaining rows on the 128x128 form when the last round
                                      would be under 60 % full (bitwise equal), 0 one launch */
-#define VGGT_TUNE_ATTN_TAIL_SPLIT 11 /* vggt_attention_fwd_ws, 8-wave D = 64 default path: 0 the row blocks of the
-                                        launch's last, partial round of workgroups run split over the keys when the
-                                        slot model says it pays (vggt_attention_split_plan), -1 never
-                                        (default; bitwise vggt_attention_fwd), parts | tail_blocks << 8 forced: the last
-                                        tail_blocks (batch, head, row block) units in parts (2..4, clamped to the
-                                        64-key tile count) workgroups each.  Env VGGT_ATTN_TAIL_SPLIT */
+#define VGGT_TUNE_ATTN_TAIL_SPLIT 11 /* vggt_attention_fwd_ws, 8-wave D = 64 default path: 0 (default) the row blocks
+                                        of the last, partial round of workgroups of ONE batch element run split over
+                                        the keys, in every batch element alike, when the slot model says it pays
+                                        (vggt_attention_split_plan on the device's CUs: an element's bits depend on
+                                        its shape and the device, not on the batch or the stream's CU mask), -1 never
+                                        (bitwise vggt_attention_fwd), parts | tail_blocks << 8 forced: the last
+                                        tail_blocks (batch, head, row block) units of the launch in parts (2..4,
+                                        clamped to the 64-key tile count) workgroups each;
+                                        VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT | parts | tail_blocks << 8 forced: the last
+                                        tail_blocks (head, row block) units of every batch element (tail_blocks
+                                        below 2^22).  Env VGGT_ATTN_TAIL_SPLIT */
+#define VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT (1 << 30)
 /* (knob 6, the persistent GEMM's DMA-placement bits, is retired: its measured-best placement is the only
    one compiled; vggt_tune(6, ...) returns VGGT_ERR_UNSUPPORTED) */
 int vggt_tune(int knob, int value);
@@ -314,20 +320,25 @@ int vggt_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride, const void
 
 /*
  * vggt_attention_fwd with a workspace, the one entry that may split keys: on
- * the 8-wave D = 64 default path (nq >= 4096) the (batch, head, 256-row block)
- * units of the launch's last, partial round of workgroups run as 2..4
+ * the 8-wave D = 64 default path (nq >= 4096) the last (head, 256-row block)
+ * units of every batch element -- those of the last, partial round of
+ * workgroups of one element launched alone on the whole device -- run as 2..4
  * workgroups each, one per contiguous range of 64-key tiles, dispatched behind
- * the whole units in the same launch; each leaves its row offsets, row sums
+ * all the whole units in the same launch; each leaves its row offsets, row sums
  * and unnormalised fp32 accumulator (m, l, O) in ws, and a second small launch
  * on the same stream merges them in a fixed order (run-to-run bitwise stable;
  * no atomics, no flags) and writes those rows of o.  All other rows are
  * bitwise those of vggt_attention_fwd.  ws: 16-byte aligned, at least
- * vggt_attention_ws_bytes(...) bytes for the same shape, stream and
- * VGGT_TUNE_ATTN_TAIL_SPLIT value (0 bytes: the launch will not split); one
- * buffer may serve every launch of a stream.  ws == NULL never splits.
+ * vggt_attention_ws_bytes(...) bytes for the same shape and
+ * VGGT_TUNE_ATTN_TAIL_SPLIT value (0 bytes: the launch will not split; the
+ * size scales with batch; `stream` is not consulted: the launch plans on the
+ * device's CU count, also on a CU-masked stream, so that the split rows and
+ * their bits depend on the element shape and the device alone); one
+ * buffer may serve every launch of a stream.  ws == NULL never splits; a
+ * buffer that is too small is VGGT_ERR_SHAPE and nothing is launched.
  * vggt_attention_split_plan is the policy alone (host arithmetic, no device
- * call): 1 and the tail size / parts for a launch on `cus` compute units
- * (two 8-wave workgroups per CU), else 0.
+ * call): 1 and the per-element tail size / parts on `cus` compute units
+ * (two 8-wave workgroups per CU), else 0; `batch` does not enter it.
  */
 int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                           int64_t k_bstride, const void* v, int64_t ldv, int64_t v_bstride, void* o, int64_t ldo,

@@ -167,7 +167,8 @@ TUNE_LINEAR_ONE_LAUNCH = 6
 TUNE_LINEAR_SPLIT_K = 7
 TUNE_LINEAR_WK = 8
 TUNE_GEMM_BALANCE = 10
-TUNE_ATTN_TAIL_SPLIT = 11  # 0 plan, -1 off, parts | tail_blocks << 8 forced (include/vggt_mi355x.h)
+TUNE_ATTN_TAIL_SPLIT = 11  # 0 plan (default), -1 off, parts | tail_blocks << 8 forced (include/vggt_mi355x.h)
+ATTN_TAIL_SPLIT_PER_ELEMENT = 1 << 30  # OR'd into a forced value: tail_blocks per batch element, not per launch
 
 
 def tune(knob: int, value: int) -> int:

@@ -55,11 +55,14 @@ struct AttnArgs {
   int batch, heads, nq, nk;
   float c;     // scale * log2(e)
   float* lse;  // optional [batch*heads*nq]: log2 sum exp2(scores * c) per row (training recompute)
-  // key-split tail (VAR & V_KEY_SPLIT only): workgroups [0, n_full) are whole units (b, h, row block) in
-  // linear order; the units from n_full on run as `parts` workgroups each, part p over the keys
-  // [p * part_tiles * 64, ...) (the last part takes the rest), and leave (m, l, O) in ws
+  // key-split tail (VAR & V_KEY_SPLIT only): of every `unit_period` consecutive (b, h, row block) units the first
+  // `full_pp` are whole and the rest the tail.  Workgroups [0, n_full) are the whole units of all periods in
+  // linear order; behind them every tail unit runs as `parts` workgroups, part p over the keys
+  // [p * part_tiles * 64, ...) (the last part takes the rest), and leaves (m, l, O) in ws -- slab
+  // (tail unit in linear order) * parts + p.  unit_period: one batch element's units, or the whole launch's
   int n_full, parts, part_tiles;
   float* ws;
+  int unit_period, full_pp;
 };
 
 // Partial of one (tail unit, part): the fp32 O accumulators in register order
@@ -161,17 +164,20 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_fwd_kernel(AttnArgs a) {
   // VAR & V_KEY_SPLIT (key-split tail): the first n_full workgroups are whole units,
   // the others one part of a tail unit each -- its keys [key0, key0 + nk); the
   // XCD remap runs within either range (dispatch follows the block index, so
-  // the whole units keep the low indices)
+  // the whole units keep the low indices).  Whole unit w is unit w % full_pp of
+  // period w / full_pp, tail unit tu unit full_pp + tu % tail_pp of period
+  // tu / tail_pp (AttnArgs); all of it wave-uniform, on the scalar unit
   constexpr bool SPLIT = (VAR & V_KEY_SPLIT) != 0;
   int bid, nk = a.nk, key0 = 0, slab = -1;
   if constexpr (SPLIT) {
     const int bx = blockIdx.x;
     if (bx < a.n_full) {
-      bid = xcd_remap(bx, a.n_full);
+      const int w = xcd_remap(bx, a.n_full);
+      bid = w / a.full_pp * a.unit_period + w % a.full_pp;
     } else {
       slab = xcd_remap(bx - a.n_full, (int)gridDim.x - a.n_full);
-      const int part = slab % a.parts;
-      bid = a.n_full + slab / a.parts;
+      const int part = slab % a.parts, tu = slab / a.parts, tail_pp = a.unit_period - a.full_pp;
+      bid = tu / tail_pp * a.unit_period + a.full_pp + tu % tail_pp;
       key0 = part * a.part_tiles * BKV;
       nk = part == a.parts - 1 ? a.nk - key0 : a.part_tiles * BKV;
     }
@@ -1104,7 +1110,8 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a, int n
   const int lane = tid & 63, c = (tid >> 6) & 7, wave = (tid >> 9) & 7, tu = tid >> 12;
   if (tu >= n_tail) return;
   const int nqb = (a.nq + SPLIT_BQ - 1) / SPLIT_BQ;
-  const int bid = a.n_full + tu;
+  const int tail_pp = a.unit_period - a.full_pp;  // the forward kernel's decode of tail unit tu
+  const int bid = tu / tail_pp * a.unit_period + a.full_pp + tu % tail_pp;
   const int qb = bid % nqb, bh = bid / nqb;
   const int h = bh % a.heads, b = bh / a.heads;
   const int r = wave * 32 + (lane & 31), hl = lane >> 5;
@@ -1130,7 +1137,9 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a, int n
   *(uint2*)(op + (c >> 2) * 32 + 8 * (c & 3) + 4 * hl) = pk;
 }
 
-inline int attn_cu_count(hipStream_t s) {
+// The CUs the launch's split plan counts: the device's, whatever CU mask the stream
+// carries -- a launch's bits depend on its shape and the device, not on its stream
+inline int attn_cu_count() {
   static int dev_cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -1138,8 +1147,7 @@ inline int attn_cu_count(hipStream_t s) {
       n = 256;
     return n;
   }();
-  const int n = vggt_stream_cu_count(s);
-  return n > 0 ? n : dev_cus;
+  return dev_cus;
 }
 
 // ---- key-split plan: the slot model (host only, no device call) -----------
@@ -1221,14 +1229,18 @@ inline void split_shape(int nt, int want, int* parts, int* part_tiles) {
 
 // Host policy of the key-split tail (see vggt_attention_fwd_ws): 1 and
 // (*tail_blocks, *parts) when a launch of this shape on `cus` CUs should run
-// the row blocks of its last, partial round of workgroups split over the keys,
-// else 0.  Pure host arithmetic: no device is touched.
+// the last *tail_blocks row-block units of every batch element split over the
+// keys, else 0.  The plan is that of one batch element alone -- the row blocks
+// of its last, partial round of workgroups -- whatever `batch` is: an element
+// gets the same split rows in the same parts alone or in any batch, so its
+// bits do not depend on what it is batched with.  Pure host arithmetic: no
+// device is touched.
 extern "C" int vggt_attention_split_plan(int batch, int heads, int nq, int nk, int D, int cus, int* tail_blocks,
                                          int* parts) {
   if (tail_blocks) *tail_blocks = 0;
   if (parts) *parts = 0;
   if (batch <= 0 || heads <= 0 || nq < 4096 || nk <= 0 || D != 64 || cus <= 0) return 0;
-  const int64_t units64 = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads * batch;
+  const int64_t units64 = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads;
   const int slots = 2 * cus, nt = (nk + BKV - 1) / BKV;
   if (units64 < slots || units64 > (1 << 24) || units64 % slots == 0 || nt < 2) return 0;
   const int units = (int)units64, tail = units % slots;
@@ -1272,26 +1284,37 @@ extern "C" int vggt_attention_split_plan(int batch, int heads, int nq, int nk, i
 
 namespace {
 // what the VGGT_TUNE_ATTN_TAIL_SPLIT knob and the plan make of a launch that takes the
-// 8-wave D = 64 default path: tail units and parts as run (0 parts: unsplit)
-void tail_split_of(int batch, int heads, int nq, int nk, int cus, int* tail, int* parts, int* part_tiles) {
-  *tail = *parts = *part_tiles = 0;
+// 8-wave D = 64 default path, as run (0 parts: unsplit): of every `period` consecutive units the last `tail`
+// in `parts` workgroups each.  The plan and the per-element forced form split within each batch element
+// (period: its units), the launch-global forced form within the whole launch (one period)
+struct TailSplit {
+  int period, periods, tail, parts, part_tiles;
+  size_t ws_bytes() const { return (size_t)periods * tail * parts * SPLIT_SLAB * sizeof(float); }
+};
+TailSplit tail_split_of(int batch, int heads, int nq, int nk) {
+  TailSplit ts = {0, 0, 0, 0, 0};
   const int knob = g_vggt_attn_tail_split;
-  const int64_t units = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads * batch;
+  const int64_t per_elem = (int64_t)((nq + SPLIT_BQ - 1) / SPLIT_BQ) * heads, units = per_elem * batch;
   const int nt = (nk + BKV - 1) / BKV;
   int t = 0, p = 0;
-  if (knob < 0 || units > (1 << 18)) return;  // (the merge kernel indexes 4096 threads per tail unit in 32 bits)
+  if (knob < 0 || units > (1 << 18)) return ts;  // (the merge kernel indexes 4096 threads per tail unit in 32 bits)
+  bool global = false;
   if (knob > 0) {
     p = knob & 0xff;
-    t = (int)std::min<int64_t>(knob >> 8, units);
-  } else if (!vggt_attention_split_plan(batch, heads, nq, nk, 64, cus, &t, &p)) {
-    return;
+    global = !(knob & VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT);
+    t = (int)std::min<int64_t>((knob & ~VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT) >> 8, global ? units : per_elem);
+  } else if (!vggt_attention_split_plan(1, heads, nq, nk, 64, attn_cu_count(), &t, &p)) {
+    return ts;
   }
   int pr, pt;
   split_shape(nt, std::min(p, 4), &pr, &pt);
-  if (pr < 2 || t <= 0) return;
-  *tail = t;
-  *parts = pr;
-  *part_tiles = pt;
+  if (pr < 2 || t <= 0) return ts;
+  ts.period = (int)(global ? units : per_elem);
+  ts.periods = global ? 1 : batch;
+  ts.tail = t;
+  ts.parts = pr;
+  ts.part_tiles = pt;
+  return ts;
 }
 
 // ---- which kernel a launch runs -------------------------------------------
@@ -1423,9 +1446,8 @@ extern "C" int vggt_attention_stamps_form(int nq, int* waves, int* var) {
 
 extern "C" size_t vggt_attention_ws_bytes(int batch, int heads, int nq, int nk, int D, void* stream) {
   if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || !attn_resolve_now(D, nq).key_split) return 0;
-  int tail, parts, pt;
-  tail_split_of(batch, heads, nq, nk, attn_cu_count((hipStream_t)stream), &tail, &parts, &pt);
-  return (size_t)tail * parts * SPLIT_SLAB * sizeof(float);
+  (void)stream;  // the split is a function of the shape, the knob and the device alone
+  return tail_split_of(batch, heads, nq, nk).ws_bytes();
 }
 
 // vggt_attention_fwd with a workspace: the only entry that may run the last, partial round of workgroups of the
@@ -1443,18 +1465,21 @@ extern "C" int vggt_attention_fwd_ws(const void* q, int64_t ldq, int64_t q_bstri
   hipStream_t s = (hipStream_t)stream;
   AttnForm f = attn_resolve_now(D, nq);
   const int nwg = attn_grid(f.nw, batch, heads, nq);
-  int tail = 0, parts = 0, pt = 0;
-  if (f.key_split && ws) tail_split_of(batch, heads, nq, nk, attn_cu_count(s), &tail, &parts, &pt);
-  if (parts < 2) return attn_launch(f, D, a, nwg, s);
-  // key-split tail: the last `tail` units as `parts` workgroups each behind the whole
-  // units, in the same launch; then the merge of their partials, on the same stream
-  if (ws_bytes < (size_t)tail * parts * SPLIT_SLAB * sizeof(float)) return VGGT_ERR_SHAPE;
+  TailSplit ts = {0, 0, 0, 0, 0};
+  if (f.key_split && ws) ts = tail_split_of(batch, heads, nq, nk);
+  if (ts.parts < 2) return attn_launch(f, D, a, nwg, s);
+  // key-split tail: the last `tail` units of every period as `parts` workgroups each behind all
+  // the whole units, in the same launch; then the merge of their partials, on the same stream
+  if (ws_bytes < ts.ws_bytes()) return VGGT_ERR_SHAPE;
+  const int tail = ts.periods * ts.tail;
   a.n_full = nwg - tail;
-  a.parts = parts;
-  a.part_tiles = pt;
+  a.parts = ts.parts;
+  a.part_tiles = ts.part_tiles;
   a.ws = (float*)ws;
+  a.unit_period = ts.period;
+  a.full_pp = ts.period - ts.tail;
   f.var |= V_KEY_SPLIT;
-  const int rc2 = attn_launch(f, D, a, a.n_full + tail * parts, s);
+  const int rc2 = attn_launch(f, D, a, a.n_full + tail * ts.parts, s);
   if (rc2 != VGGT_OK) return rc2;
   attn_split_merge_kernel<<<tail * 16, 256, 0, s>>>(a, tail);
   HIP_LAUNCH_CHECK();

@@ -54,11 +54,11 @@ const GemmKnobs g_vggt_gemm_knobs = {env_or("VGGT_GEMM_MID", 0),   env_or("VGGT_
                                      env_or("VGGT_GEMM_GM", 4) & 255, env_or("VGGT_GEMM_SPLITDMA", 1) != 0,
                                      env_or("VGGT_HEADNORM_TILE", -1)};
 // key-split tail of the global attention launch (attention.hip, vggt_attention_fwd_ws): 0 the slot-model plan,
-// -1 off (bitwise the unsplit launch), parts | tail_blocks << 8 forced (tests, A/B).  Off by default: it is faster
-// (global attention 1,725 -> 1,679 us per launch, step -0.95 ms, profiles/r12/ab_attn_tail_split.md), but a row's
-// bits then depend on the launch's shape, and the grouped-encode and sequence parity tests require that a chunk
-// encoded in a batch of two equals the same chunk encoded alone
-int g_vggt_attn_tail_split = env_or("VGGT_ATTN_TAIL_SPLIT", -1);
+// -1 off (bitwise the unsplit launch), parts | tail_blocks << 8 forced over the launch's last units, the same with
+// VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT over every batch element's last units (tests, A/B).  On by default: the plan is
+// that of one batch element on the whole device, applied to every element, so a chunk encoded in a batch of two is
+// bitwise the same chunk encoded alone (the grouped-encode and sequence parity tests require it), on any stream
+int g_vggt_attn_tail_split = env_or("VGGT_ATTN_TAIL_SPLIT", 0);
 
 extern "C" int vggt_tune(int knob, int value) {
   int prev;
@@ -107,7 +107,9 @@ extern "C" int vggt_tune(int knob, int value) {
       g_vggt_gemm_balance = value;
       return prev;
     case VGGT_TUNE_ATTN_TAIL_SPLIT:
-      if (value < -1 || (value > 0 && ((value & 0xff) < 2 || (value >> 8) < 1))) return VGGT_ERR_UNSUPPORTED;
+      if (value < -1 || value == VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT ||
+          (value > 0 && ((value & 0xff) < 2 || ((value & ~VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT) >> 8) < 1)))
+        return VGGT_ERR_UNSUPPORTED;
       prev = g_vggt_attn_tail_split;
       g_vggt_attn_tail_split = value;
       return prev;

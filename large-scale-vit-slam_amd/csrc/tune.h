@@ -10,7 +10,7 @@ extern int g_vggt_linear_split_k;    // split-K vggt_linear_f32_ws: split while 
 extern int g_vggt_linear_one_launch; // split-K vggt_linear_f32_ws: 1 combine in the same launch (default), 0 reduce launch
 extern int g_vggt_linear_wk;         // vggt_linear_f32_ws, M <= 256: in-workgroup split-K, ~this many k per wave (0: off)
 extern int g_vggt_gemm_balance;      // 1: persistent GEMMs with a partial last round split (whole rounds persistent, rest 128x128)
-extern int g_vggt_attn_tail_split;   // global attention key-split tail: 0 plan (auto), -1 off, parts | tail_blocks << 8 forced
+extern int g_vggt_attn_tail_split;   // global attention key-split tail: 0 per-element plan (default), -1 off, parts | tail_blocks << 8 forced (| bit 30: per element)
 // The GEMM dispatcher's environment-only knobs (A/B switches; read once when the library loads, no vggt_tune id;
 // gemm.hip's gemm_resolve states what each one decides)
 struct GemmKnobs {

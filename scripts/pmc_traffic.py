@@ -63,6 +63,9 @@ def main():
     ap.add_argument("write_dir")
     ap.add_argument("--kernel", default="attn_fwd_kernel")
     ap.add_argument("--grid", type=int, default=None)
+    ap.add_argument("--plus", default=None, metavar="KERNEL",
+                    help="a second kernel launched once per launch of --kernel (the key-split tail's merge): "
+                         "its traffic is added to hbm_bytes_per_launch")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     fetch_kb, nf = per_launch(a.fetch_dir, "FETCH_SIZE", a.kernel, a.grid)
@@ -72,6 +75,12 @@ def main():
            "launches": [nf, nw], "hbm_bytes_per_launch": traffic,
            "correction": "FETCH_SIZE x2 (gfx950 16-B/lane streaming reads), WRITE_SIZE x1",
            **_stamp()}
+    if a.plus:
+        pf, npf = per_launch(a.fetch_dir, "FETCH_SIZE", a.plus, None)
+        pw, npw = per_launch(a.write_dir, "WRITE_SIZE", a.plus, None)
+        res["plus"] = {"kernel": a.plus, "fetch_size_kb_raw": pf, "write_size_kb": pw, "launches": [npf, npw],
+                       "hbm_bytes_per_launch": 2.0 * pf * 1024 + pw * 1024}
+        res["hbm_bytes_per_launch"] += res["plus"]["hbm_bytes_per_launch"]
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as fh:
