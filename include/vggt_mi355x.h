@@ -582,7 +582,28 @@ int vggt_dpt_activate(const float* x, int64_t ldx, int64_t npix, int pix_per_img
  * conf_dst == NULL: conf_src holds the weights themselves; factor <= 0: no
  * confidence threshold; max_iters == 0 with both is weighted_umeyama_sim3
  * (pointAligned_wrapped_vggt.py:159-219).
- * workspace: >= vggt_irls_workspace_bytes(B), 16-B aligned, device memory.
+ * A point of weight 0 (below the threshold, confidence 0, or a Huber weight
+ * that underflowed) is skipped: it adds nothing to any sum, so its coordinates
+ * may be NaN or inf, as with the reference's boolean mask.  NaN / inf
+ * coordinates at a point that carries weight make that element's outputs NaN.
+ * NaN or negative (combined) confidences are outside the reference's domain
+ * (its median turns NaN): such a point never carries weight, and in the median
+ * it counts as larger than every non-negative value (the select orders the bit
+ * patterns).  If the median itself is NaN, every point is dropped and the
+ * element's outputs are NaN; if it is negative, no threshold applies.
+ * Rank-1 clouds (collinear points, two points): when the second singular value
+ * of the covariance is <= 2^-40 of the first (fp64 rounding noise of the
+ * sums), the rotation about the line is free and R is completed to SOME proper
+ * rotation (R R^T = I, det R = +1) that maps the source line onto the
+ * destination line; s and t are the unique ones.  The solve diagonalises
+ * Sg^T Sg, so above that threshold R is as accurate as an fp64 SVD's only to
+ * about 2^-53 (sv_0 / sv_1)^2: one fp32 ulp down to sv_1 / sv_0 ~ 4e-5 (a cloud
+ * 150 times longer than wide); a needle with extents 1 : 1e-3 : 1e-6 measured
+ * 1.5e-5 in R in a host restatement.
+ * One source position (n == 1, or all weight on coincident points, var_x == 0):
+ * no scale or rotation is defined (the reference divides 0 by 0): outputs NaN.
+ * workspace: >= vggt_irls_workspace_bytes(B), 16-B aligned, device memory; it
+ * needs no clearing between calls.
  */
 size_t vggt_irls_workspace_bytes(int B);
 int vggt_irls_sim3(const float* src, int64_t src_bs, const float* dst, int64_t dst_bs, const float* conf_src,
@@ -661,6 +682,9 @@ int vggt_nn1_pair_stats(const float* x, int64_t x_bs, const int64_t* x_len, cons
  * chunk), gt_first [B,4,4] = gt_poses[:, 0] or NULL; all fp32 contiguous device.
  * Outputs aligned_pose_enc [B,S,9]; point_transform [B,4,4] (or NULL) =
  * context ? inv(per_frame_se3[:,0]) @ extr_raw[:,0] : extr_raw[:,0].
+ * Without a context the mean is I whether or not gt_first is given (the first
+ * chunk defines the frame); with a context gt_first wins over the overlap mean,
+ * and overlap is then neither read nor checked.
  * Requires 1 <= overlap <= min(S, S_prev, 64) when the Markley path runs.
  */
 int vggt_pose_compose(const float* chunk_sim3, const float* frame_se3, const float* cam_pose_enc,

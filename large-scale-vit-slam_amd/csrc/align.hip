@@ -8,7 +8,8 @@
 //   * combined confidence c = sqrt(conf_src * conf_dst); its lower median
 //     (torch.median) by an exact 4-pass radix select over the float bits
 //     (c >= 0, so the bit pattern orders like the value); points with
-//     c < 0.5 * median get weight 0 (= the reference's boolean-mask filter);
+//     c < 0.5 * median get weight 0, and a point of weight 0 is skipped, so
+//     its coordinates may be NaN / inf (= the reference's boolean-mask filter);
 //   * each weighted Umeyama solve = two grid-wide passes (weighted centroids,
 //     then centred covariance + source variance) with per-block partial sums
 //     reduced in a fixed order in fp64, and one single-thread solve: 3x3 SVD
@@ -100,7 +101,7 @@ __global__ void irls_select(IrlsArgs a, int pass) {
 __device__ __forceinline__ float weight_at(const IrlsArgs& a, const IrlsState& st, int b, int64_t i, bool robust,
                                            float x0, float x1, float x2, float y0, float y1, float y2) {
   const float c = comb_at(a, b, i);
-  if (!(c >= st.thr)) return 0.f;
+  if (!(c >= st.thr) || c < 0.f) return 0.f;  // below the threshold, NaN or negative: not a point
   if (!robust) return c;
   // transformed = s * (src @ R^T) + t  (fp32)
   const float p0 = st.s * (x0 * st.R[0] + x1 * st.R[1] + x2 * st.R[2]) + st.t[0];
@@ -140,6 +141,7 @@ __global__ __launch_bounds__(NTH) void irls_pass1(IrlsArgs a, int robust) {
     const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2];
     const float y0 = y[3 * i], y1 = y[3 * i + 1], y2 = y[3 * i + 2];
     const double w = weight_at(a, st, b, i, robust, x0, x1, x2, y0, y1, y2);
+    if (w == 0.0) continue;  // adds nothing, whatever its coordinates (0 * NaN would be NaN)
     acc[0] += w;
     acc[1] += w * x0;
     acc[2] += w * x1;
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(NTH) void irls_pass2(IrlsArgs a, int robust) {
     const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2];
     const float y0 = y[3 * i], y1 = y[3 * i + 1], y2 = y[3 * i + 2];
     const double w = weight_at(a, st, b, i, robust, x0, x1, x2, y0, y1, y2);
+    if (w == 0.0) continue;
     const double cx0 = x0 - mx0, cx1 = x1 - mx1, cx2 = x2 - mx2;
     const double wy0 = w * (y0 - my0), wy1 = w * (y1 - my1), wy2 = w * (y2 - my2);
     acc[0] += wy0 * cx0;
@@ -254,20 +257,21 @@ __global__ void irls_solve(IrlsArgs a, int iter, int max_iters) {
     for (int j = 0; j < 10; ++j) s2[j] += p2[k * 10 + j];
   }
   const double W = s1[0];
-  if (W < 1e-6) {  // the reference raises ValueError("Total weight too small ...")
+  auto no_solution = [&]() {
     st.err = 1;
     st.done = 1;
     for (int j = 0; j < 9; ++j) a.R_out[b * 9 + j] = NAN;
     for (int j = 0; j < 3; ++j) a.t_out[b * 3 + j] = NAN;
     a.s_out[b] = NAN;
-    return;
-  }
+  };
+  if (W < 1e-6) return no_solution();  // the reference raises ValueError("Total weight too small ...")
   const double mux[3] = {s1[1] / W, s1[2] / W, s1[3] / W};
   const double muy[3] = {s1[4] / W, s1[5] / W, s1[6] / W};
   double Sg[3][3];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) Sg[i][j] = s2[3 * i + j] / W;
   const double varx = s2[9] / W;
+  if (varx == 0.0) return no_solution();  // all weight on one source position: the reference's s is 0 / 0
   // SVD Sg = U diag(sv) V^T via the eigen-decomposition of Sg^T Sg
   double A[3][3], V[3][3];
   for (int i = 0; i < 3; ++i)
@@ -296,6 +300,26 @@ __global__ void irls_solve(IrlsArgs a, int iter, int max_iters) {
     nrm = sqrt(nrm);
     sv[k] = nrm;
     for (int i = 0; i < 3; ++i) U[i][k] = nrm > 0 ? u[i] / nrm : (i == k ? 1.0 : 0.0);
+  }
+  // Rank <= 1 (collinear clouds, two points): Sg v_1 is rounding noise and its
+  // direction is not orthogonal to u_0.  Every entry of Sg is a sum of fp64
+  // products reduced through at most ceil(n / 65536) + 6 + 4 + 256 additions
+  // (thread, wave, block, the NB partials), so up to n = 2^24 it carries at most
+  // about 2^9 * 2^-53 = 2^-44 of sum w |y_c| |x_c| / W <= sqrt(var_x var_y), which is
+  // sv_0 for a rank-1 cloud; v_1's own error adds 2^-52 sv_0.  Below 2^-40 sv_0
+  // (16 x that bound) sv_1 carries no information about the rotation round
+  // u_0: take any unit vector orthogonal to u_0, from the axis u_0 is furthest from.
+  if (sv[1] <= 0x1p-40 * sv[0]) {
+    int j = 0;
+    for (int i = 1; i < 3; ++i)
+      if (fabs(U[i][0]) < fabs(U[j][0])) j = i;
+    double nrm = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      U[i][1] = (i == j ? 1.0 : 0.0) - U[j][0] * U[i][0];
+      nrm += U[i][1] * U[i][1];
+    }
+    nrm = sqrt(nrm);
+    for (int i = 0; i < 3; ++i) U[i][1] /= nrm;
   }
   U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
   U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];

@@ -6,7 +6,8 @@
 //
 // One 64-lane workgroup per batch element; lane f (stride 64) owns frame f.
 // All pose algebra in fp32 as the reference (autocast is disabled there,
-// featureAligned_vggt.py:104); the Jacobi sweeps run in fp64 and the unit
+// featureAligned_vggt.py:104), except the FoV round trip (tan, atan: fp64,
+// rounded once); the Jacobi sweeps run in fp64 and the unit
 // eigenvector is rounded to fp32 like torch.linalg.eigh's fp32 result (its
 // sign is arbitrary in both, SURVEY Appendix A.7 -- and irrelevant here: the
 // mean only enters through quat_to_mat, which is even in q).
@@ -240,13 +241,15 @@ __global__ __launch_bounds__(64) void pose_compose_kernel(
     mat_to_quat(a.r, q);
     const float* c = cb + (int64_t)f * 9;
     // pose_encoding_to_extri_intri -> intrinsics -> extri_intri_to_pose_encoding
-    const float fy = (H / 2.0f) / tanf(c[7] / 2.0f);
-    const float fx = (W / 2.0f) / tanf(c[8] / 2.0f);
+    // (in fp64, rounded once: tanf / atanf and two divisions are up to 4.5 x further from the
+    // exact value than the same fp32 steps with a correctly rounded libm)
+    const double fy = ((double)H / 2.0) / tan((double)c[7] / 2.0);
+    const double fx = ((double)W / 2.0) / tan((double)c[8] / 2.0);
     float* o = out + ((int64_t)b * S + f) * 9;
     o[0] = a.t[0]; o[1] = a.t[1]; o[2] = a.t[2];
     o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
-    o[7] = 2.0f * atanf((H / 2.0f) / fy);
-    o[8] = 2.0f * atanf((W / 2.0f) / fx);
+    o[7] = (float)(2.0 * atan(((double)H / 2.0) / fy));
+    o[8] = (float)(2.0 * atan(((double)W / 2.0) / fx));
     if (f == 0 && pt_out != nullptr) {
       // point transform (:188-195): context ? inv(per_frame_se3[:, 0]) @ ptid : ptid
       const Aff p = ctx != nullptr ? mul(inv_se3(pf), s_ptid) : s_ptid;
