@@ -666,6 +666,73 @@ int vggt_nn1_pair_stats(const float* x, int64_t x_bs, const int64_t* x_len, cons
                         void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * Point-cloud preparation before ICP (Metrics.prepare_data_for_metrics,
+ * training/training_metrics.py:264-358; csrc/points.hip; SPEC_ASSUMPTIONS.md).
+ *
+ * vggt_kth_value_f32: *out (device) = the exact k-th smallest (1-based) of the n
+ * contiguous fp32 values at x, in torch.kthvalue's order: -inf < finite < +inf <
+ * NaN (a NaN comes back, as the quiet NaN 0x7fc00000, only for ranks past the
+ * non-NaN count); -0 and +0 compare equal and +0 stands for both.  Radix select,
+ * four 8-bit passes over x, integer atomics only: a function of the multiset,
+ * bitwise repeatable, no host synchronisation.  ws: 8-byte aligned, >=
+ * vggt_kth_value_ws_bytes(n).  n < 1 or k outside [1, n]: VGGT_ERR_SHAPE.
+ */
+size_t vggt_kth_value_ws_bytes(int64_t n);
+int vggt_kth_value_f32(const float* x, int64_t n, int64_t k, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * The bilinear subsample used below is F.interpolate(mode="bilinear",
+ * align_corners=False, size=(Ho, Wo)) restated; per axis, with in -> out:
+ *   scale = (float)in / (float)out;  src = max(fmaf(scale, dst + 0.5f, -0.5f), 0);
+ *   i0 = min((int)src, in - 1);  i1 = min(i0 + 1, in - 1);
+ *   l1 = clamp(src - i0, 0, 1);  l0 = 1 - l1;
+ *   value = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d),
+ * every product and sum rounded to fp32 on its own.  Ho == H && Wo == W is a pass
+ * through (no arithmetic: a non-finite neighbour cannot enter through a zero
+ * weight); otherwise non-finite taps propagate as this arithmetic propagates them.
+ *
+ * vggt_subsample_mask_count: *count_out (device int64) = the number of output
+ * pixels, over all B * S images, where the subsample of the bool mask gt_mask
+ * (B, S, H, W; one byte a pixel, as 0 / 1 floats) exceeds 0.5: one step of the
+ * reference's subsampling-factor search (:305-306).  1 <= Ho <= H, 1 <= Wo <= W.
+ */
+int vggt_subsample_mask_count(const void* gt_mask, int B, int S, int H, int W, int Ho, int Wo, int64_t* count_out,
+                              void* stream);
+
+/*
+ * vggt_prepare_clouds: the two clouds ICP receives (:323-355), per batch element b
+ *   gt_cloud[b]   = the subsampled gt_points where the subsampled gt_mask > 0.5,
+ *   pred_cloud[b] = the subsampled predicted points where the subsampled
+ *                   (conf > *thr) mask > 0.5 and the subsampled gt_mask > 0.5,
+ * both in row-major (S, Ho, Wo) order (boolean indexing's), padded to cap_g /
+ * cap_p rows ((B, cap, 3) fp32; rows past a cap are dropped, rows past a length
+ * are left untouched), with the full counts in gt_len / pred_len (device int64[B]).
+ * The predicted points are depth (B, S, H, W) unprojected tap by tap -- ray =
+ * kinv (u, v, 1), cam = ray * depth, world = R cam + t with kinv (B, S, 3, 3) the
+ * inverse intrinsics and c2w (B, S, 3, 4) = [R | t], each 3-term dot summed left
+ * to right, unfused -- or, with depth == NULL, point_map (B, S, H, W, 3).  conf:
+ * (B, S, H, W); thr: a device scalar (vggt_kth_value_f32's out); gt_points:
+ * (B, S, H, W, 3); gt_mask: (B, S, H, W) bool bytes.  All tensors contiguous.
+ * A workgroup takes rows_per_workgroup output rows of one batch element (0 = as
+ * many as hold 4096 pixels); the result does not depend on it.
+ * phase: VGGT_PREPARE_COUNT decides every pixel, keeps the decisions in ws and
+ * writes the lengths (the clouds may be NULL); VGGT_PREPARE_SCATTER writes the
+ * clouds from the ws a COUNT call with the same arguments left;
+ * VGGT_PREPARE_ALL does both.  ws: 8-byte aligned, >=
+ * vggt_prepare_clouds_ws_bytes(B, S, Ho, Wo, rows_per_workgroup).
+ * B > 65535 or S * H * W >= 2^31 - 256: VGGT_ERR_SHAPE.
+ */
+#define VGGT_PREPARE_ALL 0
+#define VGGT_PREPARE_COUNT 1
+#define VGGT_PREPARE_SCATTER 2
+size_t vggt_prepare_clouds_ws_bytes(int B, int S, int Ho, int Wo, int rows_per_workgroup);
+int vggt_prepare_clouds(const float* depth, const float* kinv, const float* c2w, const float* point_map,
+                        const float* conf, const float* thr, const float* gt_points, const void* gt_mask, int B, int S,
+                        int H, int W, int Ho, int Wo, float* pred_cloud, int64_t cap_p, float* gt_cloud, int64_t cap_g,
+                        int64_t* pred_len, int64_t* gt_len, int rows_per_workgroup, int phase, void* ws,
+                        size_t ws_bytes, void* stream);
+
+/*
  * Per-chunk pose / Sim(3) composition of FeatureAlignedVGGT.forward
  * (featureAligned_vggt.py:96-143 and the point transform of :187-196), one
  * launch, no host synchronisation:

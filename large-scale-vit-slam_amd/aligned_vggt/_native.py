@@ -117,11 +117,17 @@ _SIGS = {
     "vggt_nn1": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "vggt_nn1_plan": [_i, _i64, _i64, _i],
     "vggt_nn1_pair_stats": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp],
+    # point-cloud preparation before ICP (csrc/points.hip)
+    "vggt_kth_value_f32": [_vp, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp],
+    "vggt_subsample_mask_count": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "vggt_prepare_clouds": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp,
+                            _vp, _i, _i, _vp, ctypes.c_size_t, _vp],
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
            "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp],
-           "vggt_nn1_workspace_bytes": [_i, _i64, _i64]}
+           "vggt_nn1_workspace_bytes": [_i, _i64, _i64], "vggt_kth_value_ws_bytes": [_i64],
+           "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i]}
 
 _lib = None
 
@@ -969,6 +975,106 @@ def nn1_pair_stats(x: torch.Tensor, y: torch.Tensor, idx: torch.Tensor, x_len=No
                                _p(out), _p(ws), ws.numel() * 8, _stream())
     _check(rc, "vggt_nn1_pair_stats")
     return out
+
+
+# ---------------------------------------------------------------- point-cloud preparation before ICP
+PREPARE_ALL, PREPARE_COUNT, PREPARE_SCATTER = 0, 1, 2
+
+
+def kth_value_ws_bytes(n: int) -> int:
+    """vggt_kth_value_ws_bytes (host arithmetic only)."""
+    return int(lib().vggt_kth_value_ws_bytes(int(n)))
+
+
+def prepare_clouds_ws_bytes(B: int, S: int, Ho: int, Wo: int, rows_per_workgroup: int = 0) -> int:
+    """vggt_prepare_clouds_ws_bytes (host arithmetic only)."""
+    return int(lib().vggt_prepare_clouds_ws_bytes(int(B), int(S), int(Ho), int(Wo), int(rows_per_workgroup)))
+
+
+def _ws_bytes(device, nbytes: int) -> torch.Tensor:
+    return torch.empty((nbytes + 7) // 8 + 1, device=device, dtype=torch.int64)
+
+
+def kth_value(x: torch.Tensor, k: int) -> torch.Tensor:
+    """vggt_kth_value_f32 on the current stream: the exact k-th smallest (1-based,
+    torch.kthvalue's order) of all elements of the fp32 tensor ``x`` as a 0-dim
+    device tensor; nothing visits the host."""
+    _dev(x, "kth_value")
+    assert x.dtype == torch.float32, "kth_value: fp32 values"
+    x = x.detach().reshape(-1)
+    x = x if x.is_contiguous() else x.contiguous()
+    n = x.numel()
+    if not 1 <= int(k) <= n:
+        raise ValueError(f"kth_value: rank {k} outside [1, {n}]")
+    out = torch.empty((), device=x.device, dtype=torch.float32)
+    L = lib()
+    ws = _ws_bytes(x.device, int(L.vggt_kth_value_ws_bytes(n)))
+    rc = L.vggt_kth_value_f32(_p(x), n, int(k), _p(out), _p(ws), ws.numel() * 8, _stream())
+    _check(rc, "vggt_kth_value_f32")
+    return out
+
+
+def _mask_bytes(mask: torch.Tensor, name: str) -> torch.Tensor:
+    _dev(mask, name)
+    assert mask.dtype in (torch.bool, torch.uint8) and mask.dim() == 4, f"{name}: (B, S, H, W) bool mask"
+    return mask if mask.is_contiguous() else mask.contiguous()
+
+
+def subsample_mask_count(gt_mask: torch.Tensor, Ho: int, Wo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vggt_subsample_mask_count: the number of (Ho, Wo) output pixels, over the whole
+    batch, where the bilinear subsample of the (B, S, H, W) bool mask exceeds 0.5,
+    as a 0-dim int64 device tensor."""
+    gt_mask = _mask_bytes(gt_mask, "subsample_mask_count")
+    B, S, H, W = gt_mask.shape
+    if out is None:
+        out = torch.empty((), device=gt_mask.device, dtype=torch.int64)
+    rc = lib().vggt_subsample_mask_count(_p(gt_mask), B, S, H, W, int(Ho), int(Wo), _p(out), _stream())
+    _check(rc, "vggt_subsample_mask_count")
+    return out
+
+
+def prepare_clouds(depth: Optional[torch.Tensor], kinv: Optional[torch.Tensor], c2w: Optional[torch.Tensor],
+                   point_map: Optional[torch.Tensor], conf: torch.Tensor, thr: torch.Tensor, gt_points: torch.Tensor,
+                   gt_mask: torch.Tensor, Ho: int, Wo: int, pred_cloud: Optional[torch.Tensor] = None,
+                   gt_cloud: Optional[torch.Tensor] = None, pred_len: Optional[torch.Tensor] = None,
+                   gt_len: Optional[torch.Tensor] = None, rows_per_workgroup: int = 0, phase: int = PREPARE_ALL,
+                   ws: Optional[torch.Tensor] = None):
+    """vggt_prepare_clouds on the current stream.  depth (B, S, H, W) with kinv
+    (B, S, 3, 3) and c2w (B, S, 3, 4), or point_map (B, S, H, W, 3); conf
+    (B, S, H, W); thr a 0-dim device tensor; gt_points (B, S, H, W, 3); gt_mask
+    (B, S, H, W) bool; all fp32 and contiguous.  pred_cloud (B, cap_p, 3) and
+    gt_cloud (B, cap_g, 3) may be None under PREPARE_COUNT.  Returns (pred_len,
+    gt_len, ws): the (B,) int64 device lengths and the workspace a later
+    PREPARE_SCATTER call with the same arguments takes."""
+    gt_mask = _mask_bytes(gt_mask, "prepare_clouds")
+    B, S, H, W = gt_mask.shape
+    dev = gt_mask.device
+    shapes = ((depth, (B, S, H, W)), (kinv, (B, S, 3, 3)), (c2w, (B, S, 3, 4)), (point_map, (B, S, H, W, 3)),
+              (conf, (B, S, H, W)), (thr, ()), (gt_points, (B, S, H, W, 3)), (pred_cloud, None), (gt_cloud, None))
+    for t, shape in shapes:
+        if t is None:
+            continue
+        _dev(t, "prepare_clouds")
+        assert t.dtype == torch.float32 and t.is_contiguous() and (shape is None or tuple(t.shape) == shape), \
+            f"prepare_clouds: contiguous fp32 tensors of the documented shapes (got {tuple(t.shape)}, want {shape})"
+    assert (depth is not None and kinv is not None and c2w is not None) or point_map is not None, \
+        "prepare_clouds: depth with kinv and c2w, or point_map"
+    for t in (pred_cloud, gt_cloud):
+        assert t is None or (t.dim() == 3 and t.shape[0] == B and t.shape[2] == 3), "prepare_clouds: (B, cap, 3) clouds"
+    if pred_len is None:
+        pred_len = torch.empty(B, device=dev, dtype=torch.int64)
+    if gt_len is None:
+        gt_len = torch.empty(B, device=dev, dtype=torch.int64)
+    L = lib()
+    if ws is None:
+        ws = _ws_bytes(dev, int(L.vggt_prepare_clouds_ws_bytes(B, S, int(Ho), int(Wo), int(rows_per_workgroup))))
+    rc = L.vggt_prepare_clouds(_p(depth), _p(kinv), _p(c2w), _p(point_map), _p(conf), _p(thr), _p(gt_points),
+                               _p(gt_mask), B, S, H, W, int(Ho), int(Wo), _p(pred_cloud),
+                               pred_cloud.shape[1] if pred_cloud is not None else 0, _p(gt_cloud),
+                               gt_cloud.shape[1] if gt_cloud is not None else 0, _p(pred_len), _p(gt_len),
+                               int(rows_per_workgroup), int(phase), _p(ws), ws.numel() * 8, _stream())
+    _check(rc, "vggt_prepare_clouds")
+    return pred_len, gt_len, ws
 
 
 # ---------------------------------------------------------------- training (backward) wrappers
