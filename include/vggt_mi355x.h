@@ -560,6 +560,55 @@ int vggt_conv2d_upsample_bf16x3(const float* x, int nimg, int hi, int wi, int C,
                                 void* stream);
 
 /*
+ * Which kernel the four convolution entry points above launch, or the error they return: host arithmetic
+ * only, no device call.  The answer is the dispatcher's own (conv_resolve in csrc/conv.hip) under the
+ * process's current VGGT_TUNE_CONV_PF2.
+ *   entry    VGGT_CONV_ENTRY_*; the geometry integers and ldx / ldy / ldys are the entry point's.  ho / wo are
+ *            read for ENTRY_UPSAMPLE only (the resize target; ci is its C, and kh / kw / stride / pad / shuffle /
+ *            ldx are not read: 3 x 3, 1, 1, 0, C); ldys for ENTRY_PRE and ENTRY_UPSAMPLE.
+ *   present  VGGT_CONV_HAS_* bits: which of y, y_hi, y_lo, res1, res2, pos the call gives.
+ * Every pointer is taken as 16-byte aligned, so the VGGT_ERR_ALIGN answers are those of the leading dimension
+ * alone (ldx % 4, for ENTRY_PRE ldx % 8).
+ * The rule, in the order the checks apply: non-positive dimensions, ci % 32, overlapping rows (ldx < ci on
+ * more than one pixel, ldy < co with y) are VGGT_ERR_SHAPE; a pixel shuffle with anything but a 1x1 stride-1
+ * unpadded kernel and no res1 / res2 / pos is VGGT_ERR_UNSUPPORTED; then alignment; then more than 2^31 - 1
+ * tiles of 128 pixels x 64 columns is VGGT_ERR_SHAPE (whichever width runs); ENTRY_PRE then asks for an
+ * output, both split halves or none and ldys >= co (VGGT_ERR_SHAPE), ldx % 8, and a map below 0x7fffff00
+ * bytes (VGGT_ERR_SHAPE).  The split forms run 128-column tiles from 128 GEMM columns (co, or s s co with a
+ * shuffle), 64-column ones above 32, else 32; vggt_conv2d_f32 always 64.  vggt_conv2d_bf16x3 gathers two
+ * deep (pf2) when VGGT_TUNE_CONV_PF2 is on and the f32 map ends below 0xffffff00 bytes.
+ * w_rows is the contract on the packed weights: the kernel reads rows [0, w_rows) of W (w_hi / w_lo) through
+ * an unbounded descriptor, so rows from co' up to w_rows must exist (and hold zeros).  w_rows is a multiple of
+ * bn and never exceeds roundup(co', 128).
+ */
+#define VGGT_CONV_ENTRY_F32 0      /* vggt_conv2d_f32             */
+#define VGGT_CONV_ENTRY_BF16X3 1   /* vggt_conv2d_bf16x3          */
+#define VGGT_CONV_ENTRY_PRE 2      /* vggt_conv2d_bf16x3_pre      */
+#define VGGT_CONV_ENTRY_UPSAMPLE 3 /* vggt_conv2d_upsample_bf16x3 */
+#define VGGT_CONV_FAMILY_F32 0      /* conv_f32_kernel                 */
+#define VGGT_CONV_FAMILY_SPLIT 1    /* conv_bf16x3_kernel<bn, pf2>     */
+#define VGGT_CONV_FAMILY_PRE 2      /* conv_pre_kernel<bn>             */
+#define VGGT_CONV_FAMILY_UPSAMPLE 3 /* conv_up_kernel<32>              */
+#define VGGT_CONV_HAS_Y 1
+#define VGGT_CONV_HAS_Y_HI 2
+#define VGGT_CONV_HAS_Y_LO 4
+#define VGGT_CONV_HAS_RES1 8
+#define VGGT_CONV_HAS_RES2 16
+#define VGGT_CONV_HAS_POS 32
+typedef struct {
+  int family;      /* VGGT_CONV_FAMILY_* */
+  int bn;          /* tile columns (tile rows: 128 pixels) */
+  int pf2;         /* split form: 1 two-deep gather, 0 one-deep */
+  int grid, lds;   /* workgroups launched, static LDS bytes */
+  unsigned xbytes; /* bytes of the input map the gather's descriptor covers (0: plain loads) */
+  int w_rows;      /* weight rows the kernel reads: tiles_n * bn */
+  int rc;          /* VGGT_OK, or the entry point's error */
+} vggt_conv_form_t;
+int vggt_conv_form(int entry, int nimg, int hi, int wi, int ci, int co, int kh, int kw, int stride, int pad,
+                   int shuffle, int ho, int wo, int64_t ldx, int64_t ldy, int64_t ldys, int present,
+                   vggt_conv_form_t* form);
+
+/*
  * DPT activate_head (ext): x [npix, ncl] NHWC with the confidence last;
  * pts[p, j] = act(x[p, j]) * scale[p / pix_per_img]  (act 0 = exp, 1 = inv_log),
  * conf[p] = 1 + exp(x[p, ncl-1]) (expp1).  scale may be NULL (depth *= chunk

@@ -57,6 +57,7 @@ _SIGS = {
     "vggt_attention_fwd_form": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_attention_stamps_form": [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_gemm_form": [_i] * 11 + [_i64] * 4 + [_i] * 3 + [_vp],
+    "vggt_conv_form": [_i] * 13 + [_i64] * 3 + [_i, _vp],
     "vggt_patch_im2col": [_vp, _i, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _i, _vp],
     "vggt_dino_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "vggt_special_tokens": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp],
@@ -775,6 +776,32 @@ def conv2d_upsample_bf16x3(x: torch.Tensor, nimg: int, hi: int, wi: int, C: int,
                                            co, int(relu_out), _p(y), _ld(y) if y is not None else 0, _p(yh), _p(yl),
                                            _ld(yh) if yh is not None else 0, int(split_relu), _stream())
     _check(rc, "vggt_conv2d_upsample_bf16x3")
+
+
+CONV_ENTRY_F32, CONV_ENTRY_BF16X3, CONV_ENTRY_PRE, CONV_ENTRY_UPSAMPLE = 0, 1, 2, 3
+CONV_HAS_Y, CONV_HAS_Y_HI, CONV_HAS_Y_LO, CONV_HAS_RES1, CONV_HAS_RES2, CONV_HAS_POS = 1, 2, 4, 8, 16, 32
+_CONV_FORM_FIELDS = ("family", "bn", "pf2", "grid", "lds", "xbytes", "w_rows", "rc")
+
+
+class _ConvForm(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint if name == "xbytes" else _i) for name in _CONV_FORM_FIELDS]
+
+
+def conv_form(entry: int, nimg: int, hi: int, wi: int, ci: int, co: int, kh: int = 1, kw: int = 1, stride: int = 1,
+              pad: int = 0, shuffle: int = 0, ho: int = 0, wo: int = 0, ldx: Optional[int] = None,
+              ldy: Optional[int] = None, ldys: Optional[int] = None, present: int = CONV_HAS_Y) -> dict:
+    """vggt_conv_form (host arithmetic only): the kernel the convolution entry point `entry` launches for
+    this geometry under the current VGGT_TUNE_CONV_PF2, as a dict of vggt_conv_form_t's fields plus "name"
+    (the kernel instantiation); "rc" is the entry point's return code for pointers that are all aligned.
+    "w_rows": the rows of the packed weights the kernel reads.  Dense leading dimensions unless given;
+    ho / wo: the resize target of CONV_ENTRY_UPSAMPLE; present: CONV_HAS_* bits."""
+    f = _ConvForm()
+    lib().vggt_conv_form(entry, nimg, hi, wi, ci, co, kh, kw, stride, pad, shuffle, ho, wo, ci if ldx is None else ldx,
+                         co if ldy is None else ldy, co if ldys is None else ldys, present, ctypes.byref(f))
+    d = {name: getattr(f, name) for name in _CONV_FORM_FIELDS}
+    d["name"] = ("conv_f32_kernel", f"conv_bf16x3_kernel<{f.bn}, {'true' if f.pf2 else 'false'}>",
+                 f"conv_pre_kernel<{f.bn}>", f"conv_up_kernel<{f.bn}>")[f.family] if f.rc == VGGT_OK else None
+    return d
 
 
 def split_act_bf16x2(x: torch.Tensor, relu: bool = False, out=None):

@@ -150,7 +150,8 @@ def _pack_conv(conv: nn.Module, transpose: bool = False):
         else:
             co, ci, kh, kw = w.shape
             wp = w.detach().float().permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
-        rows = (wp.shape[0] + 127) // 128 * 128  # (the f32 kernel needs 64, the split one 128)
+        # a kernel reads vggt_conv_form's w_rows rows (a multiple of its N tile); no form's exceeds this
+        rows = (wp.shape[0] + 127) // 128 * 128
         if rows != wp.shape[0]:
             wp = torch.cat([wp, wp.new_zeros(rows - wp.shape[0], wp.shape[1])], 0)
         wp = wp.contiguous()

@@ -1,5 +1,10 @@
-// DPT head convolutions (include/vggt_mi355x.h: vggt_conv2d_f32,
-// vggt_upsample_bilinear_f32, vggt_dpt_activate).
+// DPT head convolutions and their element-wise kernels (include/vggt_mi355x.h):
+//   vggt_conv2d_f32, vggt_conv2d_bf16x3, vggt_conv2d_bf16x3_pre   the implicit GEMM in three forms
+//   vggt_conv_form                             which kernel the four convolution entries launch (host only)
+//   vggt_split_act_bf16x2, vggt_split_bf16x2   the hi / lo split of activations / weights
+//   vggt_upsample_bilinear_f32, vggt_upsample_bilinear_split, vggt_upsample_bilinear_split_sep
+//   vggt_dpt_activate
+// (vggt_conv2d_upsample_bf16x3 and its kernel are in conv_up.hip; it resolves through conv_resolve here.)
 //
 // The reference runs the DPT heads with autocast disabled
 // (featureAligned_vggt.py:104), i.e. in fp32.  Two forms of one implicit GEMM
@@ -16,12 +21,12 @@
 // pixel-shuffle store of a stride == kernel ConvTranspose2d.
 #include <math.h>
 
-#include "common.h"
+#include "conv_tile.h"
 #include "tune.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 64, BK = 32, NT = 256;
+constexpr int BM = TILE_M, BN = 64, BK = TILE_K, NT = 256;
 
 struct ConvArgs {
   const float* x;
@@ -82,13 +87,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&a
           }
           if (a.res2) v += a.res2[(int64_t)m * a.ldr2 + co];
         }
-        if (a.y) a.y[opix * a.ldy + co] = v;
-        if (a.yh) {
-          const float sv = a.split_relu ? fmaxf(v, 0.f) : v;
-          const float hv = round_bf(sv);
-          a.yh[opix * a.ldys + co] = f2bf(hv);
-          a.yl[opix * a.ldys + co] = f2bf(sv - hv);
-        }
+        store_out(a, opix, co, v);
       }
   }
 }
@@ -98,29 +97,14 @@ __global__ __launch_bounds__(NT, 2) void conv_f32_kernel(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) float Ws[2][BN * BK];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const int M = a.nimg * a.ho * a.wo;
-  const int tiles_n = (a.ncols + BN - 1) / BN;
-  const int tiles_m = (M + BM - 1) / BM;
-  const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-  const int m0 = (t / tiles_n) * BM;
-  const int n0 = (t % tiles_n) * BN;
-  const int K = a.kh * a.kw * a.ci;
-  const int nk = K / BK;
+  const ConvTile t = conv_tile<BN>(a.nimg, a.ho, a.wo, a.ncols, a.kh, a.kw, a.ci);
+  const int M = t.M, m0 = t.m0, n0 = t.n0, K = t.K, nk = t.nk;
 
   // per-thread A rows: r = tid/8 + 32*i, channel quad c4 = tid%8
   const int c4 = tid & 7;
-  int pn[4], py[4], px[4];
-  bool pv[4];
+  PixRow p[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + (tid >> 3) + 32 * i;
-    pv[i] = m < M;
-    const int mm = pv[i] ? m : 0;
-    pn[i] = mm / (a.ho * a.wo);
-    const int rem = mm % (a.ho * a.wo);
-    py[i] = (rem / a.wo) * a.stride - a.pad;
-    px[i] = (rem % a.wo) * a.stride - a.pad;
-  }
+  for (int i = 0; i < 4; ++i) p[i] = pix_row(m0 + (tid >> 3) + 32 * i, M, a.ho, a.wo, a.stride, a.pad);
   // per-thread W rows: r = tid/8 + 32*i (i < 2)
   f32x4 ra[4], rw[2];
 
@@ -131,9 +115,9 @@ __global__ __launch_bounds__(NT, 2) void conv_f32_kernel(ConvArgs a) {
     const int ky = tap / a.kw, kx = tap % a.kw;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int iy = py[i] + ky, ix = px[i] + kx;
-      if (pv[i] && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi) {
-        f32x4 v = *(const f32x4*)(a.x + (((int64_t)pn[i] * a.hi + iy) * a.wi + ix) * a.ldx + ci0);
+      const int iy = p[i].y + ky, ix = p[i].x + kx;
+      if (p[i].ok && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi) {
+        f32x4 v = *(const f32x4*)(a.x + (((int64_t)p[i].img * a.hi + iy) * a.wi + ix) * a.ldx + ci0);
         if (a.relu_in) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -165,8 +149,7 @@ __global__ __launch_bounds__(NT, 2) void conv_f32_kernel(ConvArgs a) {
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, q = lane >> 4;
   f32x4 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc_zero(acc);
 
   load(0);
   store(0);
@@ -203,7 +186,6 @@ __global__ __launch_bounds__(NT, 2) void conv_f32_kernel(ConvArgs a) {
   conv_epilogue(a, acc, M, m0, n0, wm, wn, r16, q);
 }
 
-
 // ===========================================================================
 // Split-bf16 ("bf16x3") form of the same implicit GEMM: every fp32 operand is
 // split as x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 significant
@@ -213,98 +195,75 @@ __global__ __launch_bounds__(NT, 2) void conv_f32_kernel(ConvArgs a) {
 // slice, so the conv runs on the 2.5 PF bf16 matrix path instead of the
 // 157 TF f32 one.  Weights come pre-split (vggt_split_bf16x2); activations
 // are split on the fly after the (optional) input ReLU.
-// LDS: 64-B rows (32 bf16), swizzle chunk ^ h((row>>2)&3), h = {0,3,2,1}:
-// conflict-free ds_read_b128 fragment reads (as the GEMM ring).
+// LDS layout, DMA, fragments and the three-MFMA product: conv_tile.h.
 // ===========================================================================
-__device__ __forceinline__ int swz64(int row, int chunk) { return chunk ^ ((4 - ((row >> 2) & 3)) & 3); }
+// The split-bf16 tile of BNX columns: bytes of one bf16 A / W tile half, of a stage (Ahi, Alo, Whi, Wlo),
+// the W DMA pieces (1 KiB) per wave per half (BNX 32: waves 0-1 only), and the kernel's LDS (two stages)
+template <int BNX>
+struct SplitTile {
+  static constexpr int NTN = BNX / 32;  // 16-col fragments per wave (2 waves along N)
+  static constexpr int AT = BM * BK * 2, WT = BNX * BK * 2;
+  static constexpr int STG = 2 * AT + 2 * WT;
+  static constexpr int WPW = WT / 1024 / 4 > 0 ? WT / 1024 / 4 : 1;
+  static constexpr int LDS = 2 * STG;
+};
 
-typedef int int32x4c __attribute__((ext_vector_type(4)));
+// Per-lane byte offsets of a wave's W DMA pieces (pre-split bf16 weights, rows padded to the N tile):
+// piece p (1 KiB) of a half = rows 16p..16p+15 (64-B rows); lane -> row 16p + lane/4, LDS chunk lane%4,
+// which must hold global chunk (lane%4) ^ h(row) -- the swz64 swizzle applied on the source address
+// (the DMA image is lane-linear).
+template <int WPW>
+__device__ __forceinline__ void w_offsets(uint32_t (&woff)[WPW], int wave, int lane, int K) {
+#pragma unroll
+  for (int i = 0; i < WPW; ++i) {
+    const int row = (wave * WPW + i) * 16 + (lane >> 2);
+    woff[i] = (uint32_t)(row * K + swz64(row, lane & 3) * 8) * 2u;
+  }
+}
 
-// 16 B per lane from (rsrc, voff + soff) into LDS at the wave-uniform address
-// `lds` (+ lane * 16): buffer_load ... lds (LDS-DMA).  In asm so the
-// compiler does not drain vmcnt around it; completion is waited for
-// explicitly before the barrier that publishes the stage.
-__device__ __forceinline__ void cdma16(int32x4c rsrc, uint32_t voff, uint32_t soff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds)
-               : "memory");
+// A and B fragments of wave (wm, wn) out of one stage
+template <int BNX>
+__device__ __forceinline__ void stage_frags(const char* base, int wm, int wn, int roff, bf16x8 (&ah)[4], bf16x8 (&al)[4],
+                                            bf16x8 (&bh)[BNX / 32], bf16x8 (&bl)[BNX / 32]) {
+  typedef SplitTile<BNX> T;
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int o = (wm * 64 + mt * 16) * 64 + roff;
+    ah[mt] = *(const bf16x8*)(base + o);
+    al[mt] = *(const bf16x8*)(base + T::AT + o);
+  }
+  b_frags<T::NTN>(base + 2 * T::AT, base + 2 * T::AT + T::WT, wn, roff, bh, bl);
 }
 
 template <int BNX, bool PF2>
 __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgs a, const bf16_t* __restrict__ whi,
                                                             const bf16_t* __restrict__ wlo, uint32_t xbytes) {
-  constexpr int NTN = BNX / 32;                       // 16-col fragments per wave (2 waves along N)
-  constexpr int AT = BM * BK * 2, WT = BNX * BK * 2;  // bytes of one bf16 A / W tile
-  constexpr int STG = 2 * AT + 2 * WT;               // Ahi, Alo, Whi, Wlo
-  constexpr int WPW = WT / 1024 / 4 > 0 ? WT / 1024 / 4 : 1;  // W DMA pieces per wave per half (BNX 32: waves 0-1)
-  __shared__ __attribute__((aligned(16))) char smem[2 * STG];
+  typedef SplitTile<BNX> T;
+  constexpr int NTN = T::NTN, AT = T::AT, WT = T::WT, STG = T::STG, WPW = T::WPW;
+  __shared__ __attribute__((aligned(16))) char smem[T::LDS];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int M = a.nimg * a.ho * a.wo;
-  const int tiles_n = (a.ncols + BNX - 1) / BNX;
-  const int tiles_m = (M + BM - 1) / BM;
-  const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-  const int m0 = (t / tiles_n) * BM;
-  const int n0 = (t % tiles_n) * BNX;
-  const int K = a.kh * a.kw * a.ci;
-  const int nk = K / BK;
-  // K-step order: channel slice outer, tap inner.  Step s covers tap s % ntap
-  // and channels (s / ntap)*32 .. +32, i.e. weight columns tap*ci + slice*32
-  // (the (ky, kx, ci) weight layout is unchanged).  The ntap consecutive steps
-  // of one slice gather overlapping input windows (3x3 shifts of the same
-  // pixels and channels), so the gather hits L2 instead of re-streaming the
-  // activation from HBM once per tap.
-  const int ntap = a.kh * a.kw;
-  auto kcol = [&](int s) { return (s % ntap) * a.ci + (s / ntap) * BK; };
+  const ConvTile t = conv_tile<BNX>(a.nimg, a.ho, a.wo, a.ncols, a.kh, a.kw, a.ci);
+  const int M = t.M, m0 = t.m0, n0 = t.n0, K = t.K, nk = t.nk, ntap = t.ntap;
 
   // A: rows r = tid/8 + 32*i, fp32 channel quad c4 = tid%8 (4 K values)
   const int c4 = tid & 7;
-  int pn[4], py[4], px[4];
-  bool pv[4];
+  PixRow p[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + (tid >> 3) + 32 * i;
-    pv[i] = m < M;
-    const int mm = pv[i] ? m : 0;
-    pn[i] = mm / (a.ho * a.wo);
-    const int rem = mm % (a.ho * a.wo);
-    py[i] = (rem / a.wo) * a.stride - a.pad;
-    px[i] = (rem % a.wo) * a.stride - a.pad;
-  }
-  // W (pre-split bf16, rows padded to a multiple of 128) by LDS-DMA: piece p
-  // (1 KiB) of a half = rows 16p..16p+15 (64-B rows); lane -> row 16p + lane/4,
-  // LDS chunk lane%4, which must hold global chunk (lane%4) ^ h(row) -- the
-  // swz64 swizzle applied on the source address (the DMA image is lane-linear).
+  for (int i = 0; i < 4; ++i) p[i] = pix_row(m0 + (tid >> 3) + 32 * i, M, a.ho, a.wo, a.stride, a.pad);
   const bool wdma = wave * WPW * 1024 < WT;
   uint32_t woff[WPW];
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int row = (wave * WPW + i) * 16 + (lane >> 2);
-    const int g = swz64(row, lane & 3);
-    woff[i] = (uint32_t)(row * K + g * 8) * 2u;
-  }
-  int32x4c rwh, rwl;
-  {
-    const uint64_t bh = (uint64_t)(whi + (int64_t)n0 * K), bl = (uint64_t)(wlo + (int64_t)n0 * K);
-    rwh[0] = __builtin_amdgcn_readfirstlane((uint32_t)bh);
-    rwh[1] = __builtin_amdgcn_readfirstlane((uint32_t)(bh >> 32)) & 0xffff;
-    rwl[0] = __builtin_amdgcn_readfirstlane((uint32_t)bl);
-    rwl[1] = __builtin_amdgcn_readfirstlane((uint32_t)(bl >> 32)) & 0xffff;
-    rwh[2] = rwl[2] = -1;
-    rwh[3] = rwl[3] = 0x00020000;
-  }
+  w_offsets(woff, wave, lane, K);
+  const i32x4 rwh = make_rsrc(whi + (int64_t)n0 * K, 0xffffffffu), rwl = make_rsrc(wlo + (int64_t)n0 * K, 0xffffffffu);
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)LDS_PTR(smem));
   auto wstage = [&](int buf, int kt) {
     if (!wdma) return;
-    const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)(kcol(kt) * 2));
+    const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)(t.kcol(kt) * 2));
     const uint32_t b = lds0 + buf * STG + 2 * AT + wave * WPW * 1024;
 #pragma unroll
     for (int i = 0; i < WPW; ++i) {
-      cdma16(rwh, woff[i], soff, b + i * 1024);
-      cdma16(rwl, woff[i], soff, b + WT + i * 1024);
+      dma16(rwh, woff[i], soff, b + i * 1024);
+      dma16(rwl, woff[i], soff, b + WT + i * 1024);
     }
   };
   // A gather staged through registers, one K-step ahead: issued at the start
@@ -323,12 +282,12 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgs a, const bf
     const int ky = tap / a.kw, kx = tap % a.kw;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int iy = py[i] + ky, ix = px[i] + kx;
+      const int iy = p[i].y + ky, ix = p[i].x + kx;
       // no use of the loaded value here (the input ReLU is applied at the
       // store): the gather stays in flight for two MFMA steps
       ra[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (pv[i] && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi)
-        ra[i] = *(const f32x4*)(a.x + (((int64_t)pn[i] * a.hi + iy) * a.wi + ix) * a.ldx + ci0);
+      if (p[i].ok && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi)
+        ra[i] = *(const f32x4*)(a.x + (((int64_t)p[i].img * a.hi + iy) * a.wi + ix) * a.ldx + ci0);
     }
   };
   // PF2: the gather as raw buffer loads -- every lane issues exactly its 4
@@ -342,9 +301,9 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgs a, const bf
     const int ky = tap / a.kw, kx = tap % a.kw;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int iy = py[i] + ky, ix = px[i] + kx;
-      const bool ok = pv[i] && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi;
-      const uint32_t off = ok ? (uint32_t)((((pn[i] * a.hi + iy) * a.wi + ix) * (uint32_t)a.ldx + ci0) * 4u)
+      const int iy = p[i].y + ky, ix = p[i].x + kx;
+      const bool ok = p[i].ok && iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi;
+      const uint32_t off = ok ? (uint32_t)((((p[i].img * a.hi + iy) * a.wi + ix) * (uint32_t)a.ldx + ci0) * 4u)
                               : 0xfffffff0u;
       st.ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)off, 0, 0));
     }
@@ -375,34 +334,12 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgs a, const bf
   const int r16 = lane & 15, q = lane >> 4;
   const int roff = r16 * 64 + (swz64(r16, q) << 4);  // fragment read offset (row & 15 == r16)
   f32x4 acc[4][NTN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NTN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc_zero(acc);
 
   auto compute = [&](int cur) {
-    const char* base = smem + cur * STG;
     bf16x8 ah[4], al[4], bh[NTN], bl[NTN];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int o = (wm * 64 + mt * 16) * 64 + roff;
-      ah[mt] = *(const bf16x8*)(base + o);
-      al[mt] = *(const bf16x8*)(base + AT + o);
-    }
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) {
-      const int o = (wn * NTN * 16 + nt * 16) * 64 + roff;
-      bh[nt] = *(const bf16x8*)(base + 2 * AT + o);
-      bl[nt] = *(const bf16x8*)(base + 2 * AT + WT + o);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NTN; ++nt) {
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-      }
+    stage_frags<BNX>(smem + cur * STG, wm, wn, roff, ah, al, bh, bl);
+    mfma3(acc, ah, al, bh, bl);
   };
 
   // Per step kt (LDS buffer kt & 1): W DMA of tile kt+1 into the other
@@ -492,63 +429,37 @@ __global__ __launch_bounds__(NT, 2) void conv_bf16x3_kernel(ConvArgs a, const bf
 // ~230 VALU instructions per wave per K-step on the gather addressing, the
 // split and the LDS stores (4.75 per MFMA, VALU-issue-bound at 34% MFMA busy,
 // 148^2 x 256 -> 256: profiles r3c); here the K-step is 8 DMA pieces and two
-// address selects per wave.  Same K order, same MFMA sequence: bitwise equal
-// to conv_bf16x3_kernel.
+// address selects per wave.  Same K order, same MFMA sequence (conv_tile.h
+// mfma3): bitwise equal to conv_bf16x3_kernel.
 // ===========================================================================
 template <int BNX>
 __global__ __launch_bounds__(NT, 2) void conv_pre_kernel(ConvArgs a, const bf16_t* __restrict__ xhi,
                                                          const bf16_t* __restrict__ xlo, uint32_t xbytes,
                                                          const bf16_t* __restrict__ whi, const bf16_t* __restrict__ wlo) {
-  constexpr int NTN = BNX / 32;
-  constexpr int AT = BM * BK * 2, WT = BNX * BK * 2;
-  constexpr int STG = 2 * AT + 2 * WT;  // Ahi, Alo, Whi, Wlo
-  constexpr int WPW = WT / 1024 / 4 > 0 ? WT / 1024 / 4 : 1;
+  typedef SplitTile<BNX> T;
+  constexpr int NTN = T::NTN, AT = T::AT, WT = T::WT, STG = T::STG, WPW = T::WPW;
   constexpr int APW = AT / 1024 / 4;  // A pieces per wave per half (2)
-  __shared__ __attribute__((aligned(16))) char smem[2 * STG];
+  __shared__ __attribute__((aligned(16))) char smem[T::LDS];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int M = a.nimg * a.ho * a.wo;
-  const int tiles_n = (a.ncols + BNX - 1) / BNX;
-  const int tiles_m = (M + BM - 1) / BM;
-  const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-  const int m0 = (t / tiles_n) * BM;
-  const int n0 = (t % tiles_n) * BNX;
-  const int K = a.kh * a.kw * a.ci;
-  const int nk = K / BK;
-  const int ntap = a.kh * a.kw;
-  auto kcol = [&](int s) { return (s % ntap) * a.ci + (s / ntap) * BK; };
+  const ConvTile t = conv_tile<BNX>(a.nimg, a.ho, a.wo, a.ncols, a.kh, a.kw, a.ci);
+  const int M = t.M, m0 = t.m0, n0 = t.n0, K = t.K, nk = t.nk, ntap = t.ntap;
 
   // A pieces: rows (wave*APW + j)*16 + lane/4, LDS chunk lane%4 <- global chunk swz64(row, lane%4)
   int pb[APW], py[APW], px[APW];
 #pragma unroll
   for (int j = 0; j < APW; ++j) {
     const int row = (wave * APW + j) * 16 + (lane >> 2);
-    const int m = m0 + row;
-    const int mm = m < M ? m : 0;
-    const int img = mm / (a.ho * a.wo), rem = mm % (a.ho * a.wo);
-    py[j] = (rem / a.wo) * a.stride - a.pad;
-    px[j] = (rem % a.wo) * a.stride - a.pad;
-    pb[j] = ((img * a.hi + py[j]) * a.wi + px[j]) * (int)a.ldx + swz64(row, lane & 3) * 8;
-    if (m >= M) py[j] = -(1 << 20);  // rows past M: never inside the image (read as zeros)
+    const PixRow p = pix_row(m0 + row, M, a.ho, a.wo, a.stride, a.pad);
+    py[j] = p.ok ? p.y : -(1 << 20);  // rows past M: never inside the image (read as zeros)
+    px[j] = p.x;
+    pb[j] = ((p.img * a.hi + p.y) * a.wi + p.x) * (int)a.ldx + swz64(row, lane & 3) * 8;
   }
   uint32_t woff[WPW];
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int row = (wave * WPW + i) * 16 + (lane >> 2);
-    woff[i] = (uint32_t)(row * K + swz64(row, lane & 3) * 8) * 2u;
-  }
+  w_offsets(woff, wave, lane, K);
   const bool wdma = wave * WPW * 1024 < WT;
-  auto rsrc = [](const void* p, uint32_t bytes) {
-    int32x4c r;
-    const uint64_t b = (uint64_t)p;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) & 0xffff;
-    r[2] = (int)bytes;
-    r[3] = 0x00020000;
-    return r;
-  };
-  const int32x4c rwh = rsrc(whi + (int64_t)n0 * K, 0xffffffffu), rwl = rsrc(wlo + (int64_t)n0 * K, 0xffffffffu);
-  const int32x4c rxh = rsrc(xhi, xbytes), rxl = rsrc(xlo, xbytes);
+  const i32x4 rwh = make_rsrc(whi + (int64_t)n0 * K, 0xffffffffu), rwl = make_rsrc(wlo + (int64_t)n0 * K, 0xffffffffu);
+  const i32x4 rxh = make_rsrc(xhi, xbytes), rxl = make_rsrc(xlo, xbytes);
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)LDS_PTR(smem));
   auto stage = [&](int buf, int kt) {
     const uint32_t b = lds0 + buf * STG;
@@ -559,15 +470,15 @@ __global__ __launch_bounds__(NT, 2) void conv_pre_kernel(ConvArgs a, const bf16_
       const int iy = py[j] + ky, ix = px[j] + kx;
       const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
       const uint32_t off = ok ? (uint32_t)(pb[j] + sh) * 2u : 0xfffffff0u;
-      cdma16(rxh, off, 0, b + (wave * APW + j) * 1024);
-      cdma16(rxl, off, 0, b + AT + (wave * APW + j) * 1024);
+      dma16(rxh, off, 0, b + (wave * APW + j) * 1024);
+      dma16(rxl, off, 0, b + AT + (wave * APW + j) * 1024);
     }
     if (wdma) {
-      const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)(kcol(kt) * 2));
+      const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)(t.kcol(kt) * 2));
 #pragma unroll
       for (int i = 0; i < WPW; ++i) {
-        cdma16(rwh, woff[i], soff, b + 2 * AT + (wave * WPW + i) * 1024);
-        cdma16(rwl, woff[i], soff, b + 2 * AT + WT + (wave * WPW + i) * 1024);
+        dma16(rwh, woff[i], soff, b + 2 * AT + (wave * WPW + i) * 1024);
+        dma16(rwl, woff[i], soff, b + 2 * AT + WT + (wave * WPW + i) * 1024);
       }
     }
   };
@@ -576,36 +487,8 @@ __global__ __launch_bounds__(NT, 2) void conv_pre_kernel(ConvArgs a, const bf16_
   const int r16 = lane & 15, q = lane >> 4;
   const int roff = r16 * 64 + (swz64(r16, q) << 4);
   f32x4 acc[4][NTN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NTN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc_zero(acc);
   bf16x8 ah[4], al[4], bh[NTN], bl[NTN];
-  auto reads = [&](int cur) {
-    const char* base = smem + cur * STG;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int o = (wm * 64 + mt * 16) * 64 + roff;
-      ah[mt] = *(const bf16x8*)(base + o);
-      al[mt] = *(const bf16x8*)(base + AT + o);
-    }
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) {
-      const int o = (wn * NTN * 16 + nt * 16) * 64 + roff;
-      bh[nt] = *(const bf16x8*)(base + 2 * AT + o);
-      bl[nt] = *(const bf16x8*)(base + 2 * AT + WT + o);
-    }
-  };
-  auto mfmas = [&]() {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NTN; ++nt) {
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-      }
-  };
 
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -613,8 +496,8 @@ __global__ __launch_bounds__(NT, 2) void conv_pre_kernel(ConvArgs a, const bf16_
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
-    reads(cur);
-    mfmas();
+    stage_frags<BNX>(smem + cur * STG, wm, wn, roff, ah, al, bh, bl);
+    mfma3(acc, ah, al, bh, bl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
@@ -631,17 +514,12 @@ __global__ __launch_bounds__(256) void split_act_kernel(const float* __restrict_
     const int64_t r = i / c4n;
     const int c = (int)(i - r * c4n) * 4;
     f32x4 v = *(const f32x4*)(x + r * ldx + c);
-    float h[4];
+    if (relu) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (relu) v[j] = fmaxf(v[j], 0.f);
-      h[j] = round_bf(v[j]);
+      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
     }
     uint2 ph, pl;
-    ph.x = pack_bf2(h[0], h[1]);
-    ph.y = pack_bf2(h[2], h[3]);
-    pl.x = pack_bf2(v[0] - h[0], v[1] - h[1]);
-    pl.y = pack_bf2(v[2] - h[2], v[3] - h[3]);
+    bl_split(v, ph, pl);
     *(uint2*)(hi + r * cols + c) = ph;
     *(uint2*)(lo + r * cols + c) = pl;
   }
@@ -666,7 +544,7 @@ __global__ __launch_bounds__(256) void split_bf16x2_kernel(const float* __restri
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ x, int nimg, int hi, int wi, int C,
                                                        float* __restrict__ y, int ho, int wo,
                                                        const float* __restrict__ pos, bf16_t* __restrict__ yh,
-                                                       bf16_t* __restrict__ yl, int split_relu, int pos_sep = 0) {
+                                                       bf16_t* __restrict__ yl, int split_relu, int pos_sep) {
   const int c4n = C / 4;
   const int64_t total = (int64_t)nimg * ho * wo * c4n;
   const float sh = ho > 1 ? (float)(hi - 1) / (float)(ho - 1) : 0.f;
@@ -735,65 +613,143 @@ inline int grid_for(int64_t total) {
 
 }  // namespace
 
+// ===========================================================================
+// Dispatch.  conv_resolve maps what a call gives (ConvIn, conv_tile.h) to the error the entry returns or
+// the kernel it launches; VGGT_CONV_KERNELS lists the implicit-GEMM kernels; conv_entry runs a form.
+// vggt_conv_form exposes the resolver; tests/test_conv_form.py pins it to the checks this code replaced.
+// ===========================================================================
+enum { C_F32 = VGGT_CONV_FAMILY_F32, C_SPLIT = VGGT_CONV_FAMILY_SPLIT, C_PRE = VGGT_CONV_FAMILY_PRE };
+typedef vggt_conv_form_t ConvForm;
+
+// The checks the three implicit-GEMM entries share, in the order that fixes which code two faults at once return
+static int conv_check(const ConvIn& in) {
+  if (in.nimg <= 0 || in.hi <= 0 || in.wi <= 0 || in.ci <= 0 || in.co <= 0 || in.kh <= 0 || in.kw <= 0 ||
+      in.stride <= 0 || in.pad < 0 || in.ci % BK)
+    return VGGT_ERR_SHAPE;
+  // rows must not overlap: a pixel stride below ci (on a map of more than one pixel), an output stride below co
+  if ((in.ldx < in.ci && (int64_t)in.nimg * in.hi * in.wi > 1) || ((in.has & VGGT_CONV_HAS_Y) && in.ldy < in.co))
+    return VGGT_ERR_SHAPE;
+  if (in.shuffle && (in.kh != 1 || in.kw != 1 || in.stride != 1 || in.pad != 0 ||
+                     (in.has & (VGGT_CONV_HAS_RES1 | VGGT_CONV_HAS_RES2 | VGGT_CONV_HAS_POS))))
+    return VGGT_ERR_UNSUPPORTED;
+  if ((in.ldx % 4) || in.x_unaligned) return VGGT_ERR_ALIGN;
+  return VGGT_OK;
+}
+
+// Output size and GEMM columns of an implicit-GEMM call (after conv_check: stride > 0)
+static void conv_dims(const ConvIn& in, int& ho, int& wo, int& ncols) {
+  ho = (in.hi + 2 * in.pad - in.kh) / in.stride + 1;
+  wo = (in.wi + 2 * in.pad - in.kw) / in.stride + 1;
+  ncols = in.shuffle ? in.shuffle * in.shuffle * in.co : in.co;
+}
+
+// The one place that picks a convolution kernel.  Host arithmetic on `in` alone.
+vggt_conv_form_t conv_resolve(const ConvIn& in) {
+  ConvForm f{};
+  const bool has_y = in.has & VGGT_CONV_HAS_Y, has_hi = in.has & VGGT_CONV_HAS_Y_HI, has_lo = in.has & VGGT_CONV_HAS_Y_LO;
+  auto fail = [](int rc) { ConvForm e{}; return e.rc = rc, e; };
+  if (in.entry == VGGT_CONV_ENTRY_UPSAMPLE) {  // conv_up_kernel: tiles of 4 x 32 output pixels x all co (<= 32)
+    if (in.nimg <= 0 || in.hi <= 0 || in.wi <= 0 || in.ho <= 0 || in.wo <= 0 || in.ci <= 0 || in.ci % TILE_K ||
+        in.co <= 0 || in.co > CONV_UP_BN || (!has_y && !has_hi))
+      return fail(VGGT_ERR_SHAPE);
+    if (has_hi != has_lo || (has_y && in.ldy < in.co) || (has_hi && in.ldys < in.co)) return fail(VGGT_ERR_SHAPE);
+    if ((int64_t)31 * 9 * in.ci + 9 * in.ci > 0x3fffffff) return fail(VGGT_ERR_SHAPE);  // 32-bit weight DMA offsets
+    if (in.x_unaligned || in.w_unaligned) return fail(VGGT_ERR_ALIGN);
+    const int64_t nwg = (int64_t)in.nimg * ((in.ho + CONV_UP_R - 1) / CONV_UP_R) * ((in.wo + CONV_UP_C - 1) / CONV_UP_C);
+    if (nwg > 0x7fffffff) return fail(VGGT_ERR_SHAPE);
+    f.family = VGGT_CONV_FAMILY_UPSAMPLE, f.bn = f.w_rows = CONV_UP_BN, f.grid = (int)nwg, f.lds = CONV_UP_LDS;
+    return f;
+  }
+  if (const int rc = conv_check(in)) return fail(rc);
+  int ho, wo, ncols;
+  conv_dims(in, ho, wo, ncols);
+  const int64_t tiles_m = ((int64_t)in.nimg * ho * wo + BM - 1) / BM;
+  // the grid guard is judged on the 64-wide tile count, whichever width runs
+  if (tiles_m * ((ncols + BN - 1) / BN) > 0x7fffffff) return fail(VGGT_ERR_SHAPE);
+  const int64_t last = (int64_t)in.nimg * in.hi * in.wi - 1;  // the last pixel
+  // split forms: 128-wide N tiles from 128 GEMM columns (more MFMA work per split of the activation
+  // tile), 64 above 32, else (output_conv2, 128 -> 32) 32: no padded MFMA columns
+  f.bn = in.entry == VGGT_CONV_ENTRY_F32 ? BN : ncols >= 128 ? 128 : ncols > 32 ? 64 : 32;
+  f.lds = f.bn == 128 ? SplitTile<128>::LDS : f.bn == 32 ? SplitTile<32>::LDS : SplitTile<64>::LDS;
+  if (in.entry == VGGT_CONV_ENTRY_F32) {
+    f.family = C_F32, f.lds = 2 * (BM + BN) * BK * 4;
+  } else if (in.entry == VGGT_CONV_ENTRY_BF16X3) {
+    if (in.w_unaligned) return fail(VGGT_ERR_ALIGN);
+    // two-deep gather (buffer loads with 32-bit byte offsets) when the input spans < 4 GiB
+    const int64_t xb = last * in.ldx * 4 + (int64_t)in.ci * 4;
+    f.family = C_SPLIT, f.pf2 = xb < (int64_t)0xffffff00ll && in.pf2, f.xbytes = f.pf2 ? (uint32_t)xb : 0u;
+  } else {
+    if ((!has_y && !has_hi) || has_hi != has_lo || (has_hi && in.ldys < in.co)) return fail(VGGT_ERR_SHAPE);
+    if (in.w_unaligned || (in.ldx % 8)) return fail(VGGT_ERR_ALIGN);
+    // 32-bit byte offsets: the whole map (plus the widest tap shift) below 4 GiB
+    const int64_t xb = last * in.ldx * 2 + (int64_t)in.ci * 2;
+    if (xb >= (int64_t)0x7fffff00ll) return fail(VGGT_ERR_SHAPE);
+    f.family = C_PRE, f.xbytes = (uint32_t)xb;
+  }
+  const int tiles_n = (ncols + f.bn - 1) / f.bn;
+  f.grid = (int)(tiles_m * tiles_n), f.w_rows = tiles_n * f.bn;
+  return f;
+}
+
+namespace {
+// Every implicit-GEMM kernel the library holds, as X(family, BN, PF2)
+#define VGGT_CONV_K_C_F32(B, P) conv_f32_kernel
+#define VGGT_CONV_K_C_SPLIT(B, P) conv_bf16x3_kernel<B, P>
+#define VGGT_CONV_K_C_PRE(B, P) conv_pre_kernel<B>
+#define VGGT_CONV_KERNELS(X)                                                                           \
+  X(C_F32, 64, false) X(C_SPLIT, 32, true) X(C_SPLIT, 64, true) X(C_SPLIT, 128, true) X(C_SPLIT, 32, false) \
+  X(C_SPLIT, 64, false) X(C_SPLIT, 128, false) X(C_PRE, 32, false) X(C_PRE, 64, false) X(C_PRE, 128, false)
+
+template <int FAM, auto KERNEL>
+void conv_start(const ConvForm& f, const ConvArgs& a, const bf16_t* xl, const bf16_t* wh, const bf16_t* wl, hipStream_t s) {
+  if constexpr (FAM == C_F32) KERNEL<<<f.grid, NT, 0, s>>>(a);
+  else if constexpr (FAM == C_SPLIT) KERNEL<<<f.grid, NT, 0, s>>>(a, wh, wl, f.xbytes);
+  else KERNEL<<<f.grid, NT, 0, s>>>(a, (const bf16_t*)a.x, xl, f.xbytes, wh, wl);
+}
+
+ConvIn conv_in(int entry, int64_t ldx, int nimg, int hi, int wi, int ci, int co, int kh, int kw, int stride, int pad,
+               int shuffle, int64_t ldy, int64_t ldys, int has) {
+  ConvIn in{};
+  in.entry = entry, in.nimg = nimg, in.hi = hi, in.wi = wi, in.ci = ci, in.co = co, in.kh = kh, in.kw = kw;
+  in.stride = stride, in.pad = pad, in.shuffle = shuffle, in.ldx = ldx, in.ldy = ldy, in.ldys = ldys, in.has = has;
+  in.pf2 = g_vggt_conv_pf2;  // read per call: vggt_tune may change it
+  return in;
+}
+
+// The three implicit-GEMM entries: x is x_hi for the pre form, which also gives x_lo; w the f32 entry's
+// weights, w_hi / w_lo the split ones.  Resolve, fill the kernel's arguments, launch.
+int conv_entry(int entry, const void* x, const void* x_lo, int64_t ldx, int nimg, int hi, int wi, int ci, const float* w,
+               const void* w_hi, const void* w_lo, const float* bias, int co, int kh, int kw, int stride, int pad,
+               float* y, int64_t ldy, int relu_in, int relu_out, const float* res1, int64_t ldr1, int res1_relu,
+               const float* res2, int64_t ldr2, const float* pos, int shuffle, void* y_hi, void* y_lo, int64_t ldys,
+               int split_relu, void* stream) {
+  ConvIn in = conv_in(entry, ldx, nimg, hi, wi, ci, co, kh, kw, stride, pad, shuffle, ldy, ldys,
+                      (y ? VGGT_CONV_HAS_Y : 0) | (y_hi ? VGGT_CONV_HAS_Y_HI : 0) | (y_lo ? VGGT_CONV_HAS_Y_LO : 0) |
+                          (res1 ? VGGT_CONV_HAS_RES1 : 0) | (res2 ? VGGT_CONV_HAS_RES2 : 0) | (pos ? VGGT_CONV_HAS_POS : 0));
+  in.x_unaligned = (((uintptr_t)x | (uintptr_t)w) % 16) != 0;
+  in.w_unaligned = (((uintptr_t)x_lo | (uintptr_t)w_hi | (uintptr_t)w_lo) % 16) != 0;
+  const ConvForm f = conv_resolve(in);
+  if (f.rc != VGGT_OK) return f.rc;
+  ConvArgs a{(const float*)x, w, bias, y, res1, res2, pos, ldx, ldy, ldr1, ldr2, nimg, hi, wi, ci, 0, 0, co, kh, kw, stride,
+             pad, relu_in, relu_out, res1_relu, shuffle, 0, (bf16_t*)y_hi, (bf16_t*)y_lo, ldys, split_relu};
+  conv_dims(in, a.ho, a.wo, a.ncols);
+#define VGGT_CONV_TRY(FAM, B, P)                         \
+  if (f.family == FAM && f.bn == B && (f.pf2 != 0) == P) \
+    conv_start<FAM, VGGT_CONV_K_##FAM(B, P)>(f, a, (const bf16_t*)x_lo, (const bf16_t*)w_hi, (const bf16_t*)w_lo, (hipStream_t)stream);
+  VGGT_CONV_KERNELS(VGGT_CONV_TRY)
+#undef VGGT_CONV_TRY
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+}  // namespace
+
 extern "C" int vggt_conv2d_f32(const float* x, int64_t ldx, int nimg, int hi, int wi, int ci, const float* w,
                                const float* bias, int co, int kh, int kw, int stride, int pad, float* y, int64_t ldy,
                                int relu_in, int relu_out, const float* res1, int64_t ldr1, int res1_relu,
                                const float* res2, int64_t ldr2, const float* pos, int shuffle, void* stream) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ci <= 0 || co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
-    return VGGT_ERR_SHAPE;
-  if (ci % BK) return VGGT_ERR_SHAPE;
-  // rows must not overlap: a pixel stride below ci (on a map of more than one pixel), an output stride below co
-  if ((ldx < ci && (int64_t)nimg * hi * wi > 1) || (y && ldy < co)) return VGGT_ERR_SHAPE;
-  if (shuffle && (kh != 1 || kw != 1 || stride != 1 || pad != 0 || res1 || res2 || pos)) return VGGT_ERR_UNSUPPORTED;
-  if ((ldx % 4) || ((uintptr_t)x % 16) || ((uintptr_t)w % 16)) return VGGT_ERR_ALIGN;
-  ConvArgs a;
-  a.x = x; a.w = w; a.bias = bias; a.y = y; a.res1 = res1; a.res2 = res2; a.pos = pos;
-  a.ldx = ldx; a.ldy = ldy; a.ldr1 = ldr1; a.ldr2 = ldr2;
-  a.nimg = nimg; a.hi = hi; a.wi = wi; a.ci = ci;
-  a.ho = (hi + 2 * pad - kh) / stride + 1;
-  a.wo = (wi + 2 * pad - kw) / stride + 1;
-  a.co = co; a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
-  a.relu_in = relu_in; a.relu_out = relu_out; a.res1_relu = res1_relu;
-  a.shuffle = shuffle;
-  a.ncols = shuffle ? shuffle * shuffle * co : co;
-  a.yh = a.yl = nullptr;
-  a.ldys = 0;
-  a.split_relu = 0;
-  const int64_t M = (int64_t)nimg * a.ho * a.wo;
-  const int64_t nwg = ((M + BM - 1) / BM) * ((a.ncols + BN - 1) / BN);
-  if (nwg > 0x7fffffff) return VGGT_ERR_SHAPE;
-  conv_f32_kernel<<<(int)nwg, NT, 0, (hipStream_t)stream>>>(a);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
-}
-
-static int conv_args(ConvArgs& a, const float* x, int64_t ldx, int nimg, int hi, int wi, int ci, const float* w,
-                     const float* bias, int co, int kh, int kw, int stride, int pad, float* y, int64_t ldy, int relu_in,
-                     int relu_out, const float* res1, int64_t ldr1, int res1_relu, const float* res2, int64_t ldr2,
-                     const float* pos, int shuffle, int64_t* nwg) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ci <= 0 || co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0)
-    return VGGT_ERR_SHAPE;
-  if (ci % BK) return VGGT_ERR_SHAPE;
-  // rows must not overlap: a pixel stride below ci (on a map of more than one pixel), an output stride below co
-  if ((ldx < ci && (int64_t)nimg * hi * wi > 1) || (y && ldy < co)) return VGGT_ERR_SHAPE;
-  if (shuffle && (kh != 1 || kw != 1 || stride != 1 || pad != 0 || res1 || res2 || pos)) return VGGT_ERR_UNSUPPORTED;
-  if ((ldx % 4) || ((uintptr_t)x % 16)) return VGGT_ERR_ALIGN;
-  a.x = x; a.w = w; a.bias = bias; a.y = y; a.res1 = res1; a.res2 = res2; a.pos = pos;
-  a.ldx = ldx; a.ldy = ldy; a.ldr1 = ldr1; a.ldr2 = ldr2;
-  a.nimg = nimg; a.hi = hi; a.wi = wi; a.ci = ci;
-  a.ho = (hi + 2 * pad - kh) / stride + 1;
-  a.wo = (wi + 2 * pad - kw) / stride + 1;
-  a.co = co; a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
-  a.relu_in = relu_in; a.relu_out = relu_out; a.res1_relu = res1_relu;
-  a.shuffle = shuffle;
-  a.ncols = shuffle ? shuffle * shuffle * co : co;
-  a.yh = a.yl = nullptr;
-  a.ldys = 0;
-  a.split_relu = 0;
-  const int64_t M = (int64_t)nimg * a.ho * a.wo;
-  *nwg = ((M + BM - 1) / BM) * ((a.ncols + BN - 1) / BN);
-  if (*nwg > 0x7fffffff) return VGGT_ERR_SHAPE;
-  return VGGT_OK;
+  return conv_entry(VGGT_CONV_ENTRY_F32, x, nullptr, ldx, nimg, hi, wi, ci, w, nullptr, nullptr, bias, co, kh, kw, stride,
+                    pad, y, ldy, relu_in, relu_out, res1, ldr1, res1_relu, res2, ldr2, pos, shuffle, nullptr, nullptr, 0, 0,
+                    stream);
 }
 
 extern "C" int vggt_conv2d_bf16x3(const float* x, int64_t ldx, int nimg, int hi, int wi, int ci, const void* w_hi,
@@ -801,34 +757,9 @@ extern "C" int vggt_conv2d_bf16x3(const float* x, int64_t ldx, int nimg, int hi,
                                   float* y, int64_t ldy, int relu_in, int relu_out, const float* res1, int64_t ldr1,
                                   int res1_relu, const float* res2, int64_t ldr2, const float* pos, int shuffle,
                                   void* stream) {
-  ConvArgs a;
-  int64_t nwg;
-  const int rc = conv_args(a, x, ldx, nimg, hi, wi, ci, nullptr, bias, co, kh, kw, stride, pad, y, ldy, relu_in,
-                           relu_out, res1, ldr1, res1_relu, res2, ldr2, pos, shuffle, &nwg);
-  if (rc) return rc;
-  if (((uintptr_t)w_hi % 16) || ((uintptr_t)w_lo % 16)) return VGGT_ERR_ALIGN;
-  // 128-wide N tiles when there are at least 128 GEMM columns (more MFMA work
-  // per split of the activation tile), else 64
-  // two-deep gather (buffer loads with 32-bit byte offsets) when the input spans < 4 GiB
-  const int64_t xb = ((int64_t)nimg * hi * wi - 1) * ldx * 4 + (int64_t)ci * 4;
-  const bool pf2 = xb < (int64_t)0xffffff00ll && g_vggt_conv_pf2;
-  const uint32_t xbytes = pf2 ? (uint32_t)xb : 0u;
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t *wh = (const bf16_t*)w_hi, *wl = (const bf16_t*)w_lo;
-#define VGGT_CONV(BNX, G)                                                            \
-  (pf2 ? conv_bf16x3_kernel<BNX, true><<<(int)(G), NT, 0, s>>>(a, wh, wl, xbytes)   \
-       : conv_bf16x3_kernel<BNX, false><<<(int)(G), NT, 0, s>>>(a, wh, wl, xbytes))
-  if (a.ncols >= 128) {
-    const int64_t nw2 = (nwg / ((a.ncols + BN - 1) / BN)) * ((a.ncols + 127) / 128);
-    VGGT_CONV(128, nw2);
-  } else if (a.ncols > 32) {
-    VGGT_CONV(64, nwg);
-  } else {  // output_conv2 (128 -> 32): 32-wide N tiles, no padded MFMA columns
-    VGGT_CONV(32, nwg);
-  }
-#undef VGGT_CONV
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return conv_entry(VGGT_CONV_ENTRY_BF16X3, x, nullptr, ldx, nimg, hi, wi, ci, nullptr, w_hi, w_lo, bias, co, kh, kw,
+                    stride, pad, y, ldy, relu_in, relu_out, res1, ldr1, res1_relu, res2, ldr2, pos, shuffle, nullptr,
+                    nullptr, 0, 0, stream);
 }
 
 extern "C" int vggt_conv2d_bf16x3_pre(const void* x_hi, const void* x_lo, int64_t ldx, int nimg, int hi, int wi,
@@ -837,35 +768,23 @@ extern "C" int vggt_conv2d_bf16x3_pre(const void* x_hi, const void* x_lo, int64_
                                       const float* res1, int64_t ldr1, int res1_relu, const float* res2, int64_t ldr2,
                                       const float* pos, int shuffle, void* y_hi, void* y_lo, int64_t ldys,
                                       int split_relu, void* stream) {
-  ConvArgs a;
-  int64_t nwg;
-  const int rc = conv_args(a, (const float*)x_hi, ldx, nimg, hi, wi, ci, nullptr, bias, co, kh, kw, stride, pad, y, ldy,
-                           0, relu_out, res1, ldr1, res1_relu, res2, ldr2, pos, shuffle, &nwg);
-  if (rc) return rc;
-  if (!y && !y_hi) return VGGT_ERR_SHAPE;
-  if (!y_hi != !y_lo || (y_hi && ldys < co)) return VGGT_ERR_SHAPE;
-  a.yh = (bf16_t*)y_hi;
-  a.yl = (bf16_t*)y_lo;
-  a.ldys = ldys;
-  a.split_relu = split_relu;
-  if (((uintptr_t)x_lo % 16) || ((uintptr_t)w_hi % 16) || ((uintptr_t)w_lo % 16) || (ldx % 8)) return VGGT_ERR_ALIGN;
-  // 32-bit byte offsets: the whole map (plus the widest tap shift) below 4 GiB
-  const int64_t xb = ((int64_t)nimg * hi * wi - 1) * ldx * 2 + (int64_t)ci * 2;
-  if (xb >= (int64_t)0x7fffff00ll) return VGGT_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t *xh = (const bf16_t*)x_hi, *xl = (const bf16_t*)x_lo;
-  const bf16_t *wh = (const bf16_t*)w_hi, *wl = (const bf16_t*)w_lo;
-  if (a.ncols >= 128) {
-    const int64_t nw2 = (nwg / ((a.ncols + BN - 1) / BN)) * ((a.ncols + 127) / 128);
-    conv_pre_kernel<128><<<(int)nw2, NT, 0, s>>>(a, xh, xl, (uint32_t)xb, wh, wl);
-  } else if (a.ncols > 32) {
-    conv_pre_kernel<64><<<(int)nwg, NT, 0, s>>>(a, xh, xl, (uint32_t)xb, wh, wl);
-  } else {
-    conv_pre_kernel<32><<<(int)nwg, NT, 0, s>>>(a, xh, xl, (uint32_t)xb, wh, wl);
-  }
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return conv_entry(VGGT_CONV_ENTRY_PRE, x_hi, x_lo, ldx, nimg, hi, wi, ci, nullptr, w_hi, w_lo, bias, co, kh, kw, stride,
+                    pad, y, ldy, 0, relu_out, res1, ldr1, res1_relu, res2, ldr2, pos, shuffle, y_hi, y_lo, ldys,
+                    split_relu, stream);
 }
+
+// Which kernel the four convolution entries launch (include/vggt_mi355x.h): conv_resolve under the
+// process's gather knob, every pointer taken as aligned.  No device call.
+extern "C" int vggt_conv_form(int entry, int nimg, int hi, int wi, int ci, int co, int kh, int kw, int stride, int pad,
+                              int shuffle, int ho, int wo, int64_t ldx, int64_t ldy, int64_t ldys, int present,
+                              vggt_conv_form_t* form) {
+  if (!form || entry < VGGT_CONV_ENTRY_F32 || entry > VGGT_CONV_ENTRY_UPSAMPLE) return VGGT_ERR_UNSUPPORTED;
+  ConvIn in = conv_in(entry, ldx, nimg, hi, wi, ci, co, kh, kw, stride, pad, shuffle, ldy, ldys, present);
+  in.ho = ho, in.wo = wo;
+  *form = conv_resolve(in);
+  return form->rc;
+}
+
 
 extern "C" int vggt_split_act_bf16x2(const float* x, int64_t ldx, int64_t rows, int cols, int relu, void* hi, void* lo,
                                      void* stream) {
@@ -886,39 +805,37 @@ extern "C" int vggt_split_bf16x2(const float* x, int64_t n, void* hi, void* lo, 
   return VGGT_OK;
 }
 
-extern "C" int vggt_upsample_bilinear_f32(const float* x, int nimg, int hi, int wi, int C, float* y, int ho, int wo,
-                                          const float* pos, void* stream) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C % 4) return VGGT_ERR_SHAPE;
-  if (((uintptr_t)x | (uintptr_t)y) % 16) return VGGT_ERR_ALIGN;
-  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4)), 256, 0, (hipStream_t)stream>>>(x, nimg, hi, wi, C, y,
-                                                                                                 ho, wo, pos, nullptr,
-                                                                                                 nullptr, 0);
+// The three bilinear entries' launch.  cmod: what C must be a multiple of; shape_ok: the entry's own
+// pointer-presence rules; a16: the entry's pointers that must be 16-byte aligned, OR'd
+static int upsample_launch(const float* x, int nimg, int hi, int wi, int C, int cmod, float* y, int ho, int wo,
+                           const float* pos, int pos_sep, void* y_hi, void* y_lo, int split_relu, bool shape_ok,
+                           uintptr_t a16, void* stream) {
+  if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C % cmod || !shape_ok) return VGGT_ERR_SHAPE;
+  if (a16 % 16 || ((uintptr_t)y_hi | (uintptr_t)y_lo) % 8) return VGGT_ERR_ALIGN;
+  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4)), 256, 0, (hipStream_t)stream>>>(
+      x, nimg, hi, wi, C, y, ho, wo, pos, (bf16_t*)y_hi, (bf16_t*)y_lo, split_relu, pos_sep);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
 
+extern "C" int vggt_upsample_bilinear_f32(const float* x, int nimg, int hi, int wi, int C, float* y, int ho, int wo,
+                                          const float* pos, void* stream) {
+  return upsample_launch(x, nimg, hi, wi, C, 4, y, ho, wo, pos, 0, nullptr, nullptr, 0, true,
+                         (uintptr_t)x | (uintptr_t)y, stream);
+}
+
 extern "C" int vggt_upsample_bilinear_split(const float* x, int nimg, int hi, int wi, int C, float* y, int ho, int wo,
                                             const float* pos, void* y_hi, void* y_lo, int split_relu, void* stream) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C % 4 || (!y && !y_hi) || (!y_hi != !y_lo))
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)x | (uintptr_t)y) % 16 || ((uintptr_t)y_hi | (uintptr_t)y_lo) % 8) return VGGT_ERR_ALIGN;
-  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4)), 256, 0, (hipStream_t)stream>>>(
-      x, nimg, hi, wi, C, y, ho, wo, pos, (bf16_t*)y_hi, (bf16_t*)y_lo, split_relu);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return upsample_launch(x, nimg, hi, wi, C, 4, y, ho, wo, pos, 0, y_hi, y_lo, split_relu,
+                         (y || y_hi) && !y_hi == !y_lo, (uintptr_t)x | (uintptr_t)y, stream);
 }
 
 extern "C" int vggt_upsample_bilinear_split_sep(const float* x, int nimg, int hi, int wi, int C, float* y, int ho,
                                                 int wo, const float* pos_sep, void* y_hi, void* y_lo, int split_relu,
                                                 void* stream) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C % 8 || (!y && !y_hi) || (!y_hi != !y_lo) || !pos_sep)
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)pos_sep) % 16 || ((uintptr_t)y_hi | (uintptr_t)y_lo) % 8)
-    return VGGT_ERR_ALIGN;
-  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4)), 256, 0, (hipStream_t)stream>>>(
-      x, nimg, hi, wi, C, y, ho, wo, pos_sep, (bf16_t*)y_hi, (bf16_t*)y_lo, split_relu, 1);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return upsample_launch(x, nimg, hi, wi, C, 8, y, ho, wo, pos_sep, 1, y_hi, y_lo, split_relu,
+                         (y || y_hi) && !y_hi == !y_lo && pos_sep, (uintptr_t)x | (uintptr_t)y | (uintptr_t)pos_sep,
+                         stream);
 }
 
 extern "C" int vggt_dpt_activate(const float* x, int64_t ldx, int64_t npix, int pix_per_img, int ncl, int act,

@@ -16,32 +16,18 @@
 // patch at the tap's (ky, kx) shift.  Products and K order (channel slice
 // outer, tap inner) are those of conv_pre_kernel: split-bf16, hi.hi + hi.lo +
 // lo.hi accumulated in fp32.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-constexpr int UT_R = 4, UT_C = 32;              // output tile rows x columns (128 pixels)
+constexpr int UT_R = CONV_UP_R, UT_C = CONV_UP_C;              // output tile rows x columns (128 pixels)
 constexpr int PR = UT_R + 2, PC = UT_C + 2;     // patch 6 x 34
 constexpr int PP = PR * PC;                     // 204 patch pixels
 constexpr int CS = 32;                          // channels per slice (one 32-deep K step per tap)
 constexpr int PATCH = PP * CS * 2;              // bytes of one bf16 patch half
 constexpr int UNT = 256;
 constexpr int NTAP = 9;
-
-// 64-B rows (32 bf16), swizzle chunk ^ h((row >> 2) & 3): conflict-free
-// ds_read_b128 for any 16 consecutive rows (conv.hip swz64)
-__device__ __forceinline__ int uswz(int row, int chunk) { return chunk ^ ((4 - ((row >> 2) & 3)) & 3); }
-
-typedef int i32x4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void udma16(i32x4u rsrc, uint32_t voff, uint32_t soff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds)
-               : "memory");
-}
+static_assert(UT_R * UT_C == TILE_M && CS == TILE_K, "conv_tile.h's fragment geometry");
 
 struct UpConvArgs {
   const float* x;        // source map [nimg, hi, wi, C] f32 (row stride C)
@@ -63,6 +49,7 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
   constexpr int WPW = WPIECES / 4;                    // per wave
   static_assert(WPW * 4 == WPIECES, "weight pieces split evenly over the 4 waves");
   __shared__ __attribute__((aligned(16))) char smem[2 * PATCH + 2 * NTAP * WT];
+  static_assert(BNX == CONV_UP_BN && sizeof(smem) == CONV_UP_LDS, "what conv_resolve reports");
   char* const ph = smem;
   char* const pl = smem + PATCH;
   const int tid = threadIdx.x;
@@ -79,17 +66,8 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
 
   // weight pieces: piece q (0..WPIECES-1) of a slice = half q / (WPIECES/2),
   // tap (q % (WPIECES/2)) / (WT/1024), rows 16 * ((q % (WPIECES/2)) % (WT/1024)) + lane/4
-  // (64-B rows), LDS chunk lane%4 <- global chunk uswz(row, lane%4) (swizzle on the source)
-  auto rsrc = [](const void* p) {
-    i32x4u r;
-    const uint64_t b = (uint64_t)p;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) & 0xffff;
-    r[2] = -1;
-    r[3] = 0x00020000;
-    return r;
-  };
-  const i32x4u rwh = rsrc(whi), rwl = rsrc(wlo);
+  // (64-B rows), LDS chunk lane%4 <- global chunk swz64(row, lane%4) (swizzle on the source)
+  const i32x4 rwh = make_rsrc(whi, 0xffffffffu), rwl = make_rsrc(wlo, 0xffffffffu);
   uint32_t woff[WPW];
   bool wlo_piece[WPW];
   uint32_t wdst[WPW];
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
     const int hl = q / (WPIECES / 2), qq = q % (WPIECES / 2);
     const int tap = qq / (WT / 1024), sub = qq % (WT / 1024);
     const int row = sub * 16 + (lane >> 2);
-    woff[i] = (uint32_t)(row * K + tap * C + uswz(row, lane & 3) * 8) * 2u;
+    woff[i] = (uint32_t)(row * K + tap * C + swz64(row, lane & 3) * 8) * 2u;
     wlo_piece[i] = hl != 0;
     wdst[i] = lds0 + 2 * PATCH + (hl * NTAP + tap) * WT + sub * 1024;
   }
@@ -115,19 +93,16 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
     const int r = wm * 64 + mt * 16 + r16;
     pbase[mt] = (r >> 5) * PC + (r & 31);
   }
-  const int roff_w = r16 * 64 + (uswz(r16, qc) << 4);
+  const int roff_w = r16 * 64 + (swz64(r16, qc) << 4);
   f32x4 acc[4][NTN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NTN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  acc_zero(acc);
 
   const int nslice = C / CS;
   for (int s = 0; s < nslice; ++s) {
     // this slice's 9 weight tiles by LDS-DMA (in flight during the patch build)
     const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)(s * CS * 2));
 #pragma unroll
-    for (int i = 0; i < WPW; ++i) udma16(wlo_piece[i] ? rwl : rwh, woff[i], soff, wdst[i]);
+    for (int i = 0; i < WPW; ++i) dma16(wlo_piece[i] ? rwl : rwh, woff[i], soff, wdst[i]);
     // the resized + positional + split patch: item = (patch pixel, 8-channel chunk)
     for (int it = tid; it < PP * 4; it += UNT) {
       const int pidx = it >> 2, cc = it & 3;
@@ -162,7 +137,7 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
         hv = uint4{hw[0], hw[1], hw[2], hw[3]};
         lv = uint4{lw[0], lw[1], lw[2], lw[3]};
       }
-      const int off = pidx * 64 + (uswz(pidx, cc) << 4);
+      const int off = pidx * 64 + (swz64(pidx, cc) << 4);
       *(uint4*)(ph + off) = hv;
       *(uint4*)(pl + off) = lv;
     }
@@ -176,24 +151,12 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         const int pp = pbase[mt] + sh_;
-        const int o = pp * 64 + (uswz(pp, qc) << 4);
+        const int o = pp * 64 + (swz64(pp, qc) << 4);
         ah[mt] = *(const bf16x8*)(ph + o);
         al[mt] = *(const bf16x8*)(pl + o);
       }
-#pragma unroll
-      for (int nt = 0; nt < NTN; ++nt) {
-        const int o = (wn * NTN * 16 + nt * 16) * 64 + roff_w;
-        bh[nt] = *(const bf16x8*)(wb + o);
-        bl[nt] = *(const bf16x8*)(wb + NTAP * WT + o);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NTN; ++nt) {
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-        }
+      b_frags<NTN>(wb, wb + NTAP * WT, wn, roff_w, bh, bl);
+      mfma3(acc, ah, al, bh, bl);
     }
     __syncthreads();  // every fragment read of this slice's patch / weights done
   }
@@ -215,13 +178,7 @@ __global__ __launch_bounds__(UNT, 2) void conv_up_kernel(UpConvArgs a, const bf1
         const int64_t opix = ((int64_t)img * a.ho + oy) * a.wo + ox;
         float v = acc[mt][nt][i] + bv;
         if (a.relu_out) v = fmaxf(v, 0.f);
-        if (a.y) a.y[opix * a.ldy + n] = v;
-        if (a.yh) {
-          const float sv = a.split_relu ? fmaxf(v, 0.f) : v;
-          const float hv = round_bf(sv);
-          a.yh[opix * a.ldys + n] = f2bf(hv);
-          a.yl[opix * a.ldys + n] = f2bf(sv - hv);
-        }
+        store_out(a, opix, n, v);
       }
   }
 }
@@ -232,33 +189,18 @@ extern "C" int vggt_conv2d_upsample_bf16x3(const float* x, int nimg, int hi, int
                                            int ho, int wo, const void* w_hi, const void* w_lo, const float* bias,
                                            int co, int relu_out, float* y, int64_t ldy, void* y_hi, void* y_lo,
                                            int64_t ldys, int split_relu, void* stream) {
-  if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C <= 0 || C % CS || co <= 0 || co > 32)
-    return VGGT_ERR_SHAPE;
-  if (!y && !y_hi) return VGGT_ERR_SHAPE;
-  if (!y_hi != !y_lo || (y && ldy < co) || (y_hi && ldys < co)) return VGGT_ERR_SHAPE;
-  if ((int64_t)31 * 9 * C + 9 * C > 0x3fffffff) return VGGT_ERR_SHAPE;
-  if (((uintptr_t)x | (uintptr_t)pos_sep) % 16 || ((uintptr_t)w_hi | (uintptr_t)w_lo) % 16) return VGGT_ERR_ALIGN;
-  UpConvArgs a;
-  a.x = x;
-  a.pos_sep = pos_sep;
-  a.bias = bias;
-  a.y = y;
-  a.yh = (bf16_t*)y_hi;
-  a.yl = (bf16_t*)y_lo;
-  a.ldy = ldy;
-  a.ldys = ldys;
-  a.nimg = nimg;
-  a.hi = hi;
-  a.wi = wi;
-  a.C = C;
-  a.ho = ho;
-  a.wo = wo;
-  a.co = co;
-  a.relu_out = relu_out;
-  a.split_relu = split_relu;
-  const int64_t nwg = (int64_t)nimg * ((ho + UT_R - 1) / UT_R) * ((wo + UT_C - 1) / UT_C);
-  if (nwg > 0x7fffffff) return VGGT_ERR_SHAPE;
-  conv_up_kernel<32><<<(int)nwg, UNT, 0, (hipStream_t)stream>>>(a, (const bf16_t*)w_hi, (const bf16_t*)w_lo);
+  // the checks and the grid: conv_resolve (conv.hip), family fused-upsample
+  ConvIn in{};
+  in.entry = VGGT_CONV_ENTRY_UPSAMPLE, in.nimg = nimg, in.hi = hi, in.wi = wi, in.ci = C, in.co = co;
+  in.ho = ho, in.wo = wo, in.ldy = ldy, in.ldys = ldys;
+  in.has = (y ? VGGT_CONV_HAS_Y : 0) | (y_hi ? VGGT_CONV_HAS_Y_HI : 0) | (y_lo ? VGGT_CONV_HAS_Y_LO : 0);
+  in.x_unaligned = (((uintptr_t)x | (uintptr_t)pos_sep) % 16) != 0;
+  in.w_unaligned = (((uintptr_t)w_hi | (uintptr_t)w_lo) % 16) != 0;
+  const vggt_conv_form_t f = conv_resolve(in);
+  if (f.rc != VGGT_OK) return f.rc;
+  const UpConvArgs a{x,  pos_sep, bias, y,  (bf16_t*)y_hi, (bf16_t*)y_lo, ldy,      ldys,      nimg,
+                     hi, wi,      C,    ho, wo,            co,            relu_out, split_relu};
+  conv_up_kernel<CONV_UP_BN><<<f.grid, UNT, 0, (hipStream_t)stream>>>(a, (const bf16_t*)w_hi, (const bf16_t*)w_lo);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }

@@ -20,7 +20,7 @@ def _declared():
 
 def test_header_declares_entry_points():
     names = _declared()
-    assert {"vggt_gemm_bf16", "vggt_gemm_form", "vggt_attention_fwd", "vggt_layernorm", "vggt_headnorm_rope"} <= names
+    assert {"vggt_gemm_bf16", "vggt_gemm_form", "vggt_conv_form", "vggt_attention_fwd", "vggt_layernorm", "vggt_headnorm_rope"} <= names
 
 
 def test_library_exports_every_declared_symbol():

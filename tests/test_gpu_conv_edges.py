@@ -18,7 +18,8 @@ that): a NaN that leaks in shows in the output.
 Which kernel a case reaches: conv2d_f32 -> conv_f32_kernel (128 x 64 tiles); conv2d_bf16x3 ->
 conv_bf16x3_kernel<BNX, PF2> and conv2d_bf16x3_pre -> conv_pre_kernel<BNX> with BNX = 128 for
 ncols >= 128, 64 for 32 < ncols < 128, 32 for ncols <= 32; PF2 = VGGT_TUNE_CONV_PF2 (two-deep gather with
-its 1 / 2 / 3-step tail: nk = kh*kw*ci/32 odd and >= 3 takes the 3-step one).  `_reach` restates it.
+its 1 / 2 / 3-step tail: nk = kh*kw*ci/32 odd and >= 3 takes the 3-step one).  `_reach` asks the library
+(vggt_conv_form) and adds the tail.
 
 Tolerances (none is a measured constant, except dpt_activate's device function error, see `ulp`):
   exact     part 1 / part 3 inputs: x = s (m + q 2^-10), s = +-1, m in {1, 2}, q in {0..3}, ~10 % zeros,
@@ -143,15 +144,21 @@ def _geom(name):
 
 
 def _reach(g, form):
-    """The kernel a form launches for a geometry (vggt_conv2d_* dispatch), for the printed figures."""
-    if form == "f32":
-        return "conv_f32_kernel"
-    bnx = 128 if g["ncols"] >= 128 else 64 if g["ncols"] > 32 else 32
-    if form == "pre":
-        return f"conv_pre_kernel<{bnx}>"
+    """The kernel a form launches for a geometry: the library's own answer (vggt_conv_form, host arithmetic,
+    which tests/test_conv_form.py pins to the dispatch rules), plus the tail of the two-deep gather's K loop,
+    which is this test's knowledge of nk."""
+    from aligned_vggt import _native as Nat
+    entry = {"f32": Nat.CONV_ENTRY_F32, "pre": Nat.CONV_ENTRY_PRE}.get(form, Nat.CONV_ENTRY_BF16X3)
+    prev = Nat.tune(Nat.TUNE_CONV_PF2, 0 if form == "pf1" else 1)
+    try:
+        f = Nat.conv_form(entry, g["nimg"], g["hi"], g["wi"], g["ci"], g["co"], g["kh"], g["kw"], g["stride"], g["pad"],
+                          g["shuffle"])
+    finally:
+        Nat.tune(Nat.TUNE_CONV_PF2, prev)
+    assert f["rc"] == 0, (g, form, f)
     nk = g["K"] // 32
-    tail = "" if form == "pf1" else f", {3 if nk % 2 and nk >= 3 else 2 if nk % 2 == 0 else 1}-step tail"
-    return f"conv_bf16x3_kernel<{bnx}, {'true' if form == 'pf2' else 'false'}>{tail}"
+    tail = "" if form != "pf2" else f", {3 if nk % 2 and nk >= 3 else 2 if nk % 2 == 0 else 1}-step tail"
+    return f["name"] + tail
 
 
 def test_cases_reach_every_path():
@@ -904,6 +911,13 @@ def _rc_conv(Nat, api, *, ci=32, co=8, kh=1, kw=1, ldx=None, ldy=None, shuffle=0
                                       P(outs[2]) if split[1] else Z, ldys, 0, st)
     torch.cuda.synchronize()
     clean = all(_same(o.cpu(), torch.full(o.shape, SENT).to(o.dtype)) for o in outs)
+    # the host-only query with the same integers (these buffers are all 16-byte aligned) answers the same code
+    has = (Nat.CONV_HAS_Y if y or api != "pre" else 0) | (Nat.CONV_HAS_RES1 if res1 else 0) | (Nat.CONV_HAS_POS if pos else 0)
+    if api == "pre":
+        has |= (Nat.CONV_HAS_Y_HI if split[0] else 0) | (Nat.CONV_HAS_Y_LO if split[1] else 0)
+    entry = {"f32": Nat.CONV_ENTRY_F32, "bf16x3": Nat.CONV_ENTRY_BF16X3, "pre": Nat.CONV_ENTRY_PRE}[api]
+    q = Nat.conv_form(entry, 1, hi, wi, ci, co, kh, kw, 1, 0, shuffle, ldx=ldx, ldy=ldy, ldys=ldys, present=has)
+    assert q["rc"] == rc, f"{api}: vggt_conv_form answers {q['rc']}, the entry point {rc}"
     return rc, clean
 
 
