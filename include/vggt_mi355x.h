@@ -728,6 +728,11 @@ int vggt_nn1_pair_stats(const float* x, int64_t x_bs, const int64_t* x_len, cons
  */
 size_t vggt_kth_value_ws_bytes(int64_t n);
 int vggt_kth_value_f32(const float* x, int64_t n, int64_t k, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The same select with the 1-based rank read from *k (device int64, 8-byte aligned) when the
+ * launch runs.  A rank of 0 means "skip" and a rank outside [1, n] selects nothing: *out is
+ * then the quiet NaN. */
+int vggt_kth_value_f32_devrank(const float* x, int64_t n, const int64_t* k, float* out, void* ws, size_t ws_bytes,
+                               void* stream);
 
 /*
  * The bilinear subsample used below is F.interpolate(mode="bilinear",
@@ -953,6 +958,62 @@ int vggt_wgrad_bias_f32(const float* dy, int64_t ldy, const float* x, int64_t ld
 size_t vggt_batch_dot_workspace_bytes(int B, int64_t n);
 int vggt_batch_dot_f32(const float* a, const float* c, int64_t bs, int B, int64_t n, float* out, void* ws,
                        size_t ws_bytes, void* stream);
+
+/* ======================================================================
+ * Training losses -- the depth term of MultitaskLoss (training/loss.py:
+ * compute_depth_loss :308-351, filter_by_quantile :421-457; csrc/loss.hip;
+ * aligned_vggt/training/loss.py).  pred, conf, gt: (B, S, H, W) contiguous
+ * fp32; mask: (B, S, H, W) bool bytes.  n = the number of set mask pixels.
+ * Every branch the reference takes on n, on the threshold or on the
+ * surviving count is taken on the device: no entry synchronises with the
+ * host.  B * S * H * W > 100,000,000 (the reference's random-subsample
+ * branch): VGGT_ERR_UNSUPPORTED.  Rows are read 128 bits per lane when
+ * the float pointers are 16-byte and the mask 4-byte aligned, element by
+ * element otherwise; H * W need not be a multiple of 4.
+ *
+ * vggt_depth_loss_values: amax[f] = the maximum of conf over frame f of the
+ * B * S (NaN propagates, as torch.amax); *n_out (device int64) = n;
+ *   val = |logf(max(pred, 1e-8f)) - logf(max(gt', 1e-8f))| * (conf / max(amax[f], 1e-8f))
+ * at set pixels, gt' = gt with NaN and +-inf replaced by 0, and the quiet
+ * NaN 0x7fc00000 at unset ones (NaN sorts last in torch.kthvalue's order: a
+ * rank <= n over val selects what the reference selects over its gathered
+ * vector).  max(x, c) keeps a NaN x, as torch.clamp_min.  ws: 16-byte
+ * aligned, >= vggt_depth_loss_ws_bytes(B, S, H, W) (shared by the entries).
+ *
+ * vggt_depth_loss_reduce: from val and *n.  k = round_half_even(valid_range *
+ * (n - 1)) + 1 (Python's round on the double product), or 0 when valid_range
+ * <= 0 or n <= 1000; thr' = min(k-th smallest of val, 100) (a NaN stays);
+ * m = #(min(val, 100) < thr').  *loss and the branch (state.kind):
+ *   VGGT_DEPTH_LOSS_SKIPPED    n < 100: 0;
+ *   VGGT_DEPTH_LOSS_FILTERED   k != 0 and m > 1000: the mean of the m kept min(val, 100);
+ *   VGGT_DEPTH_LOSS_CLAMPED    k != 0 otherwise: the mean of min(val, 100) over the n;
+ *   VGGT_DEPTH_LOSS_UNCLAMPED  k == 0: the mean of val over the n,
+ * where a NaN or +-inf term counts as 0 (and still counts in the
+ * denominator) and every term is clamped to +-100: check_and_fix_inf_nan
+ * before the mean.  fp64 sums in a fixed order (per-workgroup partials, one
+ * combining pass): two runs are bitwise equal.  state: 8-byte aligned,
+ * VGGT_DEPTH_LOSS_STATE_BYTES: int64 n, m, k, kind; double denom (m or n; 0
+ * when skipped); float thr' (NaN when k == 0); 4 bytes of padding.
+ *
+ * vggt_depth_loss_bwd: dpred = *grad_loss * sign(log p - log g') * conf_n / p
+ * / denom at the pixels that contribute, p = max(pred, 1e-8f), recomputed
+ * from the inputs, amax and state; 0 at unset, filtered-out and non-finite
+ * pixels, where pred < 1e-8f, where |val| > 100, and everywhere when skipped.
+ * ====================================================================== */
+#define VGGT_DEPTH_LOSS_SKIPPED 0
+#define VGGT_DEPTH_LOSS_FILTERED 1
+#define VGGT_DEPTH_LOSS_CLAMPED 2
+#define VGGT_DEPTH_LOSS_UNCLAMPED 3
+#define VGGT_DEPTH_LOSS_STATE_BYTES 48
+size_t vggt_depth_loss_ws_bytes(int B, int S, int H, int W);
+int vggt_depth_loss_values(const float* pred, const float* conf, const float* gt, const void* mask, int B, int S,
+                           int H, int W, float* val, float* amax, int64_t* n_out, void* ws, size_t ws_bytes,
+                           void* stream);
+int vggt_depth_loss_reduce(const float* val, const int64_t* n, int B, int S, int H, int W, double valid_range,
+                           float* loss, void* state, void* ws, size_t ws_bytes, void* stream);
+int vggt_depth_loss_bwd(const float* pred, const float* conf, const float* gt, const void* mask, const float* amax,
+                        const void* state, const float* grad_loss, int B, int S, int H, int W, float* dpred,
+                        void* stream);
 
 /* MFMA peak probe (diagnostic; BASELINE.md §2 asks for a measured MFMA microbenchmark with its clock):
  * nwg workgroups of 4 waves issue iters x 8 v_mfma_f32_32x32x16_bf16 each on the bf16 operands

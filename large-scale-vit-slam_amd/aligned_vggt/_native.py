@@ -123,12 +123,17 @@ _SIGS = {
     "vggt_subsample_mask_count": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "vggt_prepare_clouds": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp,
                             _vp, _i, _i, _vp, ctypes.c_size_t, _vp],
+    "vggt_kth_value_f32_devrank": [_vp, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    # training losses (csrc/loss.hip)
+    "vggt_depth_loss_values": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    "vggt_depth_loss_reduce": [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    "vggt_depth_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
            "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp],
            "vggt_nn1_workspace_bytes": [_i, _i64, _i64], "vggt_kth_value_ws_bytes": [_i64],
-           "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i]}
+           "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i], "vggt_depth_loss_ws_bytes": [_i, _i, _i, _i]}
 
 _lib = None
 
@@ -1102,6 +1107,117 @@ def prepare_clouds(depth: Optional[torch.Tensor], kinv: Optional[torch.Tensor], 
                                int(rows_per_workgroup), int(phase), _p(ws), ws.numel() * 8, _stream())
     _check(rc, "vggt_prepare_clouds")
     return pred_len, gt_len, ws
+
+
+# ---------------------------------------------------------------- training losses (csrc/loss.hip)
+DEPTH_LOSS_SKIPPED, DEPTH_LOSS_FILTERED, DEPTH_LOSS_CLAMPED, DEPTH_LOSS_UNCLAMPED = 0, 1, 2, 3
+DEPTH_LOSS_STATE_WORDS = 6  # VGGT_DEPTH_LOSS_STATE_BYTES / 8
+
+
+def kth_value_devrank(x: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+    """vggt_kth_value_f32_devrank on the current stream: kth_value with the 1-based
+    rank read from the 0-dim int64 device tensor ``k`` when the launch runs; a rank
+    of 0 (or outside [1, n]) gives NaN."""
+    _dev(x, "kth_value_devrank")
+    _dev(k, "kth_value_devrank")
+    assert x.dtype == torch.float32 and k.dtype == torch.int64 and k.numel() == 1, \
+        "kth_value_devrank: fp32 values, one int64 rank"
+    x = x.detach().reshape(-1)
+    x = x if x.is_contiguous() else x.contiguous()
+    n = x.numel()
+    if n < 1:
+        raise ValueError("kth_value_devrank: no values")
+    out = torch.empty((), device=x.device, dtype=torch.float32)
+    L = lib()
+    ws = _ws_bytes(x.device, int(L.vggt_kth_value_ws_bytes(n)))
+    rc = L.vggt_kth_value_f32_devrank(_p(x), n, _p(k), _p(out), _p(ws), ws.numel() * 8, _stream())
+    _check(rc, "vggt_kth_value_f32_devrank")
+    return out
+
+
+def depth_loss_ws_bytes(B: int, S: int, H: int, W: int) -> int:
+    """vggt_depth_loss_ws_bytes (host arithmetic only)."""
+    return int(lib().vggt_depth_loss_ws_bytes(int(B), int(S), int(H), int(W)))
+
+
+def _depth_loss_inputs(name: str, mask: torch.Tensor, *tensors):
+    mask = _mask_bytes(mask, name)
+    for t in tensors:
+        _dev(t, name)
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == mask.shape, \
+            f"{name}: contiguous fp32 (B, S, H, W) tensors (got {tuple(t.shape)} {t.dtype}, mask {tuple(mask.shape)})"
+    return mask
+
+
+def depth_loss_values(pred: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor,
+                      val: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """vggt_depth_loss_values on the current stream: (B, S, H, W) fp32 pred, conf, gt
+    and bool mask -> (val (B, S, H, W), amax (B, S), n 0-dim int64, ws); ``ws`` is the
+    workspace depth_loss_reduce takes."""
+    mask = _depth_loss_inputs("depth_loss_values", mask, pred, conf, gt)
+    B, S, H, W = mask.shape
+    dev = mask.device
+    if val is None:
+        val = torch.empty(B, S, H, W, device=dev, dtype=torch.float32)
+    _depth_loss_inputs("depth_loss_values", mask, val)
+    amax = torch.empty(B, S, device=dev, dtype=torch.float32)
+    n = torch.empty((), device=dev, dtype=torch.int64)
+    L = lib()
+    if ws is None:
+        ws = _ws_bytes(dev, int(L.vggt_depth_loss_ws_bytes(B, S, H, W)))
+    rc = L.vggt_depth_loss_values(_p(pred), _p(conf), _p(gt), _p(mask), B, S, H, W, _p(val), _p(amax), _p(n), _p(ws),
+                                  ws.numel() * 8, _stream())
+    _check(rc, "vggt_depth_loss_values")
+    return val, amax, n, ws
+
+
+def depth_loss_reduce(val: torch.Tensor, n: torch.Tensor, valid_range: float, ws: Optional[torch.Tensor] = None):
+    """vggt_depth_loss_reduce on the current stream: val (B, S, H, W) fp32 and the
+    0-dim int64 ``n`` -> (loss 0-dim fp32, state (DEPTH_LOSS_STATE_WORDS,) int64:
+    see depth_loss_state)."""
+    _dev(val, "depth_loss_reduce")
+    _dev(n, "depth_loss_reduce")
+    assert val.dtype == torch.float32 and val.is_contiguous() and val.dim() == 4, "depth_loss_reduce: (B, S, H, W) fp32"
+    assert n.dtype == torch.int64 and n.numel() == 1, "depth_loss_reduce: one int64 count"
+    B, S, H, W = val.shape
+    loss = torch.empty((), device=val.device, dtype=torch.float32)
+    state = torch.empty(DEPTH_LOSS_STATE_WORDS, device=val.device, dtype=torch.int64)
+    L = lib()
+    if ws is None:
+        ws = _ws_bytes(val.device, int(L.vggt_depth_loss_ws_bytes(B, S, H, W)))
+    rc = L.vggt_depth_loss_reduce(_p(val), _p(n), B, S, H, W, float(valid_range), _p(loss), _p(state), _p(ws),
+                                  ws.numel() * 8, _stream())
+    _check(rc, "vggt_depth_loss_reduce")
+    return loss, state
+
+
+def depth_loss_state(state: torch.Tensor) -> dict:
+    """The state words of depth_loss_reduce on the host (this one synchronises):
+    n, m, k, kind (DEPTH_LOSS_*), denom and thr (thr', fp32)."""
+    s = state.detach().cpu()
+    n, m, k, kind = (int(v) for v in s[:4])
+    return {"n": n, "m": m, "k": k, "kind": kind, "denom": float(s[4:5].view(torch.float64)[0]),
+            "thr": float(s[5:6].view(torch.float32)[0])}
+
+
+def depth_loss_bwd(pred: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, amax: torch.Tensor,
+                   state: torch.Tensor, grad_loss: torch.Tensor, dpred: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vggt_depth_loss_bwd on the current stream: d loss / d pred (B, S, H, W) fp32
+    from the forward's inputs, amax and state and the 0-dim fp32 upstream gradient."""
+    mask = _depth_loss_inputs("depth_loss_bwd", mask, pred, conf, gt)
+    B, S, H, W = mask.shape
+    for t in (amax, state, grad_loss):
+        _dev(t, "depth_loss_bwd")
+    assert amax.dtype == torch.float32 and amax.is_contiguous() and amax.numel() == B * S
+    assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() == DEPTH_LOSS_STATE_WORDS
+    assert grad_loss.dtype == torch.float32 and grad_loss.numel() == 1
+    if dpred is None:
+        dpred = torch.empty(B, S, H, W, device=mask.device, dtype=torch.float32)
+    _depth_loss_inputs("depth_loss_bwd", mask, dpred)
+    rc = lib().vggt_depth_loss_bwd(_p(pred), _p(conf), _p(gt), _p(mask), _p(amax), _p(state), _p(grad_loss), B, S, H,
+                                   W, _p(dpred), _stream())
+    _check(rc, "vggt_depth_loss_bwd")
+    return dpred
 
 
 # ---------------------------------------------------------------- training (backward) wrappers

@@ -9,7 +9,8 @@
 //   global atomics into the pass's 256 counters.  A one-workgroup launch then scans the 256 counters, picks the
 //   digit that holds the remaining rank, and leaves (prefix, rank) in ws for the next pass; after the fourth it
 //   turns the key back into the float.  The host never sees any of it.  Integer sums only: the result is a
-//   function of the multiset and two runs are bitwise equal.
+//   function of the multiset and two runs are bitwise equal.  vggt_kth_value_f32_devrank is the same select with
+//   the rank read from device memory (the depth loss's quantile, loss.hip): only the init kernel differs.
 //
 // vggt_subsample_mask_count: how many output pixels of the bilinear subsample (F.interpolate, align_corners =
 //   False) of a bool mask exceed 0.5: one step of the reference's subsampling-factor search.
@@ -142,6 +143,29 @@ __global__ void kth_init_kernel(KthState* __restrict__ state, unsigned long long
   state->rank = k;
   state->prefix = 0;
   state->pad = 0;
+}
+// The rank from device memory; outside [1, n] (0: "no quantile") nothing is selected and *out is NaN.
+__global__ void kth_init_devrank_kernel(KthState* __restrict__ state, const long long* __restrict__ k, long long n,
+                                        float* __restrict__ out) {
+  const long long rank = *k;
+  const bool ok = rank >= 1 && rank <= n;
+  state->rank = ok ? (unsigned long long)rank : 0ull;  // rank 0 falls in no bin: the picks leave *out alone
+  state->prefix = 0;
+  state->pad = 0;
+  if (!ok) *out = __uint_as_float(0x7fc00000u);
+}
+
+// The four histogram / pick rounds, after the state is initialised.
+int kth_passes(const float* x, int64_t n, float* out, unsigned long long* hist, KthState* state, hipStream_t st) {
+  const int64_t want = (n + (int64_t)KTH_THREADS * KTH_PER_THREAD - 1) / ((int64_t)KTH_THREADS * KTH_PER_THREAD);
+  const int blocks = (int)(want < 1 ? 1 : (want > KTH_MAX_BLOCKS ? KTH_MAX_BLOCKS : want));
+  for (int pass = 0; pass < KTH_PASSES; ++pass) {
+    kth_hist_kernel<<<blocks, KTH_THREADS, 0, st>>>(x, n, pass, hist, state);
+    HIP_LAUNCH_CHECK();
+    kth_pick_kernel<<<1, KTH_BINS, 0, st>>>(hist, pass, state, out);
+    HIP_LAUNCH_CHECK();
+  }
+  return VGGT_OK;
 }
 
 // ------------------------------------------------------------------------------------------ bilinear subsample
@@ -456,15 +480,21 @@ extern "C" int vggt_kth_value_f32(const float* x, int64_t n, int64_t k, float* o
   if (hipMemsetAsync(hist, 0, KTH_HIST_BYTES, st) != hipSuccess) return VGGT_ERR_HIP;
   kth_init_kernel<<<1, 1, 0, st>>>(state, (unsigned long long)k);
   HIP_LAUNCH_CHECK();
-  const int64_t want = (n + (int64_t)KTH_THREADS * KTH_PER_THREAD - 1) / ((int64_t)KTH_THREADS * KTH_PER_THREAD);
-  const int blocks = (int)(want < 1 ? 1 : (want > KTH_MAX_BLOCKS ? KTH_MAX_BLOCKS : want));
-  for (int pass = 0; pass < KTH_PASSES; ++pass) {
-    kth_hist_kernel<<<blocks, KTH_THREADS, 0, st>>>(x, n, pass, hist, state);
-    HIP_LAUNCH_CHECK();
-    kth_pick_kernel<<<1, KTH_BINS, 0, st>>>(hist, pass, state, out);
-    HIP_LAUNCH_CHECK();
-  }
-  return VGGT_OK;
+  return kth_passes(x, n, out, hist, state, st);
+}
+
+extern "C" int vggt_kth_value_f32_devrank(const float* x, int64_t n, const int64_t* k, float* out, void* ws,
+                                          size_t ws_bytes, void* stream) {
+  if (n < 1) return VGGT_ERR_SHAPE;
+  if (!x || !k || !out || !ws || ws_bytes < KTH_WS_BYTES) return VGGT_ERR_SHAPE;
+  if ((uintptr_t)ws % 8 || (uintptr_t)x % 4 || (uintptr_t)out % 4 || (uintptr_t)k % 8) return VGGT_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* hist = (unsigned long long*)ws;
+  KthState* state = (KthState*)((char*)ws + KTH_HIST_BYTES);
+  if (hipMemsetAsync(hist, 0, KTH_HIST_BYTES, st) != hipSuccess) return VGGT_ERR_HIP;
+  kth_init_devrank_kernel<<<1, 1, 0, st>>>(state, (const long long*)k, (long long)n, out);
+  HIP_LAUNCH_CHECK();
+  return kth_passes(x, n, out, hist, state, st);
 }
 
 extern "C" int vggt_subsample_mask_count(const void* gt_mask, int B, int S, int H, int W, int Ho, int Wo,
