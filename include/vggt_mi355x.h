@@ -1015,6 +1015,44 @@ int vggt_depth_loss_bwd(const float* pred, const float* conf, const float* gt, c
                         const void* state, const float* grad_loss, int B, int S, int H, int W, float* dpred,
                         void* stream);
 
+/* ======================================================================
+ * GT scale alignment -- the reference's scale_align_from_depths
+ * (utils/alignment.py:244-323; csrc/gt_align.hip): per batch element b the
+ * weighted median argmin_a sum_i w_i |a x_i - y_i| over its n = S * H * W
+ * pixels.  pred (x), conf, gt (y): fp32; mask (m): one byte per pixel;
+ * element b of each starts bstride elements after element b - 1.
+ *
+ *   cnt = sum m;  mean = (float)(sum_fp64(y * m) / max(cnt, 1)), the sum in
+ *   a fixed order that depends on n alone;  min_depth = 0.1f * mean;
+ *   per pixel, every operation rounded to fp32 on its own (max keeps a NaN):
+ *     w = m * conf * (1 / max(max(y, min_depth), 1e-6f));  sign = x < 0 ? -1 : 1;
+ *     x_pos = x * sign;  r = (y * sign) / max(x_pos, 1e-6f);  w_eff = w * x_pos;
+ *   a w_eff that is NaN, +-inf or negative counts as 0;
+ *   wmax = the largest w_eff;  e = the integer with ldexp(wmax, e) in
+ *   (2^35, 2^36] (0 when wmax == 0);  q = rint(ldexp((double)w_eff, e)), uint64;
+ *   r* = the smallest r of the multiset with 2 * sum_{r_i <= r*} q_i >= sum q
+ *   in vggt_kth_value_f32's order (-inf < finite < +inf < NaN, -0 == +0): the
+ *   reference's searchsorted(cumsum, 0.5 * total, "left"), a total of 0
+ *   selecting the smallest r;  scale_out[b] = r* <= 0 ? -r* : r*.
+ *
+ * Integer sums only: the result is a function of the inputs alone, bitwise
+ * repeatable and independent of the other elements.  No host
+ * synchronisation.  scale_out: B device floats.  state_out: B records of
+ * VGGT_DEPTH_SCALE_STATE_BYTES, 8-byte aligned: int64 cnt; uint64 sum q, sum
+ * q over r < r*, sum q over r <= r*; float mean; int32 e; uint32 key of r*;
+ * uint32 bits of wmax.  Pixels are read 128 bits per lane when the float
+ * pointers are 16-byte and the mask 4-byte aligned (and bstride % 4 == 0
+ * when B > 1), element by element otherwise.  ws: 16-byte aligned, >=
+ * vggt_depth_scale_ws_bytes(B, n).  B < 1, B > 65535, n < 1, bstride < n
+ * with B > 1, a null pointer, a misaligned or short ws: VGGT_ERR_SHAPE;
+ * n > 100,000,000: VGGT_ERR_UNSUPPORTED; pred, conf, gt or scale_out not
+ * 4-byte aligned, or state_out not 8-byte aligned: VGGT_ERR_ALIGN.
+ * ====================================================================== */
+#define VGGT_DEPTH_SCALE_STATE_BYTES 48
+size_t vggt_depth_scale_ws_bytes(int B, int64_t n);
+int vggt_depth_scale_l1(const float* pred, const float* conf, const float* gt, const void* mask, int B, int64_t n,
+                        int64_t bstride, float* scale_out, void* state_out, void* ws, size_t ws_bytes, void* stream);
+
 /* MFMA peak probe (diagnostic; BASELINE.md §2 asks for a measured MFMA microbenchmark with its clock):
  * nwg workgroups of 4 waves issue iters x 8 v_mfma_f32_32x32x16_bf16 each on the bf16 operands
  * (nwg * 256 * 16 elements: random or zeros), 32768 FLOP per MFMA; stamps[4 * wg] = s_memtime before /

@@ -128,12 +128,15 @@ _SIGS = {
     "vggt_depth_loss_values": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "vggt_depth_loss_reduce": [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     "vggt_depth_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    # GT scale alignment (csrc/gt_align.hip)
+    "vggt_depth_scale_l1": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
            "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp],
            "vggt_nn1_workspace_bytes": [_i, _i64, _i64], "vggt_kth_value_ws_bytes": [_i64],
-           "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i], "vggt_depth_loss_ws_bytes": [_i, _i, _i, _i]}
+           "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i], "vggt_depth_loss_ws_bytes": [_i, _i, _i, _i],
+           "vggt_depth_scale_ws_bytes": [_i, _i64]}
 
 _lib = None
 
@@ -1218,6 +1221,52 @@ def depth_loss_bwd(pred: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, mas
                                    W, _p(dpred), _stream())
     _check(rc, "vggt_depth_loss_bwd")
     return dpred
+
+
+# ---------------------------------------------------------------- GT scale alignment (csrc/gt_align.hip)
+DEPTH_SCALE_STATE_WORDS = 6  # VGGT_DEPTH_SCALE_STATE_BYTES / 8
+
+
+def depth_scale_ws_bytes(B: int, n: int) -> int:
+    """vggt_depth_scale_ws_bytes (host arithmetic only)."""
+    return int(lib().vggt_depth_scale_ws_bytes(int(B), int(n)))
+
+
+def depth_scale_l1(pred: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor):
+    """vggt_depth_scale_l1 on the current stream: pred, conf, gt fp32 and a bool mask,
+    each B x n elements with the batch first and contiguous -> (scales (B,) fp32, state
+    (B, DEPTH_SCALE_STATE_WORDS) int64: see depth_scale_state).  Nothing visits the host."""
+    B = pred.shape[0]
+    n = pred[0].numel()
+    for t in (pred, conf, gt, mask):
+        _dev(t, "depth_scale_l1")
+        assert t.shape[0] == B and t[0].numel() == n and t.is_contiguous(), \
+            "depth_scale_l1: contiguous tensors of B x n elements"
+    assert pred.dtype == conf.dtype == gt.dtype == torch.float32, "depth_scale_l1: fp32 pred, conf and gt"
+    assert mask.dtype in (torch.bool, torch.uint8), "depth_scale_l1: bool mask"
+    dev = pred.device
+    scales = torch.empty(B, device=dev, dtype=torch.float32)
+    state = torch.empty(B, DEPTH_SCALE_STATE_WORDS, device=dev, dtype=torch.int64)
+    L = lib()
+    ws = _ws_bytes(dev, int(L.vggt_depth_scale_ws_bytes(B, n)))  # 0 bytes: the call names the shape's error
+    rc = L.vggt_depth_scale_l1(_p(pred), _p(conf), _p(gt), _p(mask), B, n, n, _p(scales), _p(state), _p(ws),
+                               ws.numel() * 8, _stream())
+    _check(rc, "vggt_depth_scale_l1")
+    return scales, state
+
+
+def depth_scale_state(state: torch.Tensor) -> list:
+    """The state records of depth_scale_l1 on the host (this one synchronises): per
+    element cnt, total (sum q), below and through (sum q over r < r*, r <= r*), mean
+    (fp32), e, key (the selected ratio's key) and wmax (fp32)."""
+    s = state.detach().cpu().reshape(-1, DEPTH_SCALE_STATE_WORDS)
+    out = []
+    for row in s:
+        f = row[4:6].view(torch.float32)
+        i = row[4:6].view(torch.int32)
+        out.append({"cnt": int(row[0]), "total": int(row[1]), "below": int(row[2]), "through": int(row[3]),
+                    "mean": float(f[0]), "e": int(i[1]), "key": int(i[2]) & 0xffffffff, "wmax": float(f[3])})
+    return out
 
 
 # ---------------------------------------------------------------- training (backward) wrappers

@@ -8,9 +8,15 @@ Two kinds of callers:
     data.py:108-153): closed-form Umeyama / Horn and the L1/LSE scale
     alignments -- host-side numpy/torch exactly as the reference (small,
     once per sequence), pinned by tests/golden/{alignment_utils,
-    scale_alignment}.npz.
+    scale_alignment}.npz;
+  * a training step with ``gt_alignment_type: scale_from_depths`` runs
+    ``scale_align_from_depths`` on the step's device tensors, between the model
+    and the loss: there the weighted median is the HIP kernel
+    ``vggt_depth_scale_l1`` (csrc/gt_align.hip) and nothing visits the host.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -127,9 +133,64 @@ def scale_alignment_from_poses(predictions: dict, batch: dict, seq_width: int = 
     predictions["alignment_scales"] = scales
 
 
-@torch.no_grad()
+def _gt_align_kernel_applies(d_pred, conf, d_gt, mask) -> bool:
+    """All four on the device, fp32 values and a bool mask; VGGT_GT_ALIGN=torch (read
+    per call) keeps the torch chain."""
+    if os.environ.get("VGGT_GT_ALIGN", "") == "torch":
+        return False
+    return (all(t.is_cuda for t in (d_pred, conf, d_gt, mask)) and d_pred.dtype == torch.float32
+            and conf.dtype == torch.float32 and d_gt.dtype == torch.float32 and mask.dtype == torch.bool)
+
+
+def _scale_batch_(t: torch.Tensor, scales: torch.Tensor) -> None:
+    """t[b] *= scales[b] in place.  The scale is a constant of the graph: a tensor
+    autograd tracks takes torch's in-place multiply, which it records; any other
+    fp32 tensor with contiguous per-batch blocks takes vggt_scale_f32.  That kernel
+    writes through the raw pointer and does not bump the tensor's version counter:
+    a tensor without requires_grad that another op saved for its backward would
+    change without autograd noticing (the step's outputs here are not saved so)."""
+    if ((t.requires_grad and torch.is_grad_enabled()) or t.dtype != torch.float32 or not t[0].is_contiguous()
+            or not t.is_cuda):
+        t *= scales.view(-1, *([1] * (t.dim() - 1)))
+    else:
+        from .. import _native
+        _native.scale_(t, scales)
+
+
+def _scale_align_from_depths_device(predictions: dict, batch: dict) -> None:
+    """The kernel path (csrc/gt_align.hip): the weighted median by radix select on
+    the device, the scale applied from device memory; no host synchronisation."""
+    from .. import _native
+    d_pred = predictions["depth"]
+    B, S, H, W, _ = d_pred.shape
+    N = S * H * W
+    with torch.no_grad():
+        flat = [t.detach().reshape(B, N).contiguous() for t in
+                (d_pred, predictions["depth_conf"], batch["depths"], batch["point_masks"])]
+        scales, _state = _native.depth_scale_l1(*flat)
+    # outside no_grad, as the reference's in-place multiplies (:315-321): autograd sees them
+    _scale_batch_(predictions["depth"], scales)
+    if "world_points" in predictions:
+        _scale_batch_(predictions["world_points"], scales)
+    if "pose_enc" in predictions:
+        predictions["pose_enc"][..., :3] *= scales[:, None, None]
+    predictions["alignment_scales"] = list(scales.unbind(0))
+
+
 def scale_align_from_depths(predictions: dict, batch: dict) -> None:
-    """alignment.py:244-323: per-batch weighted-median (L1-optimal) depth scale."""
+    """alignment.py:244-323: per-batch weighted-median (L1-optimal) depth scale.
+    Device fp32 tensors take the kernel path (``alignment_scales`` is then a list of
+    0-dim device tensors and nothing visits the host); host tensors, other dtypes,
+    mixed placements and VGGT_GT_ALIGN=torch take the torch chain."""
+    if _gt_align_kernel_applies(predictions["depth"], predictions["depth_conf"], batch["depths"],
+                                batch["point_masks"]):
+        return _scale_align_from_depths_device(predictions, batch)
+    return _scale_align_from_depths_torch(predictions, batch)
+
+
+@torch.no_grad()
+def _scale_align_from_depths_torch(predictions: dict, batch: dict) -> None:
+    """The reference's chain of torch ops, on whatever device the tensors are."""
     d_pred, conf, d_gt, mask = predictions["depth"], predictions["depth_conf"], batch["depths"], batch["point_masks"]
     B, S, H, W, _ = d_pred.shape
     N = S * H * W
