@@ -812,6 +812,32 @@ int vggt_pose_compose(const float* chunk_sim3, const float* frame_se3, const flo
                       const float* ctx_pose_enc, int S_prev, const float* gt_first, int B, int S, int overlap, int H,
                       int W, float* aligned_pose_enc, float* point_transform, void* stream);
 
+/*
+ * Per-chunk pose algebra of the pose-aligned VGGT (poseAligned_wrapped_vggt.py
+ * :74-130, :171-177) in one launch, one 64-lane workgroup per batch element:
+ *   extr  = pose_encoding_to_extri(cam_pose_enc) @ inv(extr_raw[:,0]);
+ *   scale = gt ? | sum x.y / sum x^2 | over the S x 3 translations, x = extr's,
+ *           y = those of gt @ inv(gt[:,0]) (scale_lse_solver; x, y and the sums in
+ *           fp64 from the raw encodings, the quotient rounded to fp32 once; 0/0
+ *           gives NaN, which is kept) : 1;
+ *   extr[:, :, :3, 3] *= scale;
+ *   mean  = I (no context) | gt[:,0] (context and gt, not centred) | Markley
+ *           mean over the overlap of inv(extr[k]) @
+ *           pose_encoding_to_extri(ctx_pose_enc[S_prev-ov+k]) (ov == 1: the one
+ *           transform);
+ *   aligned_pose_enc = extri_intri_to_pose_encoding(extr @ mean).
+ * cam_pose_enc [B,S,9], ctx_pose_enc [B,S_prev,9] = context["pose_enc"][-1] or
+ * NULL (first chunk), gt [B,S,3,4] = gt_poses or NULL; all fp32 contiguous
+ * device.  Outputs aligned_pose_enc [B,S,9]; point_transform [B,4,4] (or NULL) =
+ * context ? inv(mean) @ extr_raw[:,0] : extr_raw[:,0]; scales [B].
+ * VGGT_ERR_SHAPE (nothing written): non-positive sizes, a NULL required pointer,
+ * gt with S == 1, overlap outside [1, min(S, S_prev, 64)] when the overlap path
+ * runs (context without gt; otherwise overlap is neither read nor checked).
+ */
+int vggt_pose_align(const float* cam_pose_enc, const float* ctx_pose_enc, int S_prev, const float* gt, int B, int S,
+                    int overlap, int H, int W, float* aligned_pose_enc, float* point_transform, float* scales,
+                    void* stream);
+
 /* ======================================================================
  * Training (backward) entry points -- alignment-head training, SURVEY.md §8f
  * row 4: train_featureAlignedVGGT_vkitti.yaml freezes the aggregator, camera

@@ -89,6 +89,7 @@ _SIGS = {
     "vggt_sim3_points": [_vp, _i64, _i, _i64, _vp, _vp, _vp, _i64, _vp],
     "vggt_scale_f32": [_vp, _i64, _i, _i64, _vp, _vp],
     "vggt_pose_compose": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "vggt_pose_align": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     # training (backward) entry points
     "vggt_attention_fwd_lse": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i, _i, _i,
                                _i, _i, _f, _vp],
@@ -920,6 +921,31 @@ def pose_compose(chunk_sim3: torch.Tensor, frame_se3: torch.Tensor, cam_pose_enc
                                  B, S, int(overlap), H, W, _p(out), _p(pt), _stream())
     _check(rc, "vggt_pose_compose")
     return out, pt
+
+
+def pose_align(cam_pose_enc: torch.Tensor, ctx_pose_enc: Optional[torch.Tensor], gt_poses: Optional[torch.Tensor],
+               overlap: int, image_hw, want_point_transform: bool = True):
+    """poseAligned_wrapped_vggt.py:74-130 (+ the point transform of :171-177) in
+    one launch -> (aligned_pose_enc (B,S,9), point_transform (B,4,4) or None,
+    scales (B,)).  cam_pose_enc (B,S,9), ctx_pose_enc (B,S_prev,9) or None,
+    gt_poses (B,S,3,4) or None: contiguous fp32 device tensors."""
+    _dev(cam_pose_enc, "pose_align")
+    dev = cam_pose_enc.device
+    B, S = cam_pose_enc.shape[:2]
+    assert cam_pose_enc.shape == (B, S, 9)
+    assert ctx_pose_enc is None or (ctx_pose_enc.dim() == 3 and ctx_pose_enc.shape[0] == B and ctx_pose_enc.shape[2] == 9)
+    assert gt_poses is None or gt_poses.shape == (B, S, 3, 4)
+    for t in (cam_pose_enc, ctx_pose_enc, gt_poses):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev), \
+            "pose_align: contiguous fp32 tensors on one device"
+    out = torch.empty(B, S, 9, device=dev)
+    pt = torch.empty(B, 4, 4, device=dev) if want_point_transform else None
+    scales = torch.empty(B, device=dev)
+    rc = lib().vggt_pose_align(_p(cam_pose_enc), _p(ctx_pose_enc), ctx_pose_enc.shape[1] if ctx_pose_enc is not None else 0,
+                               _p(gt_poses), B, S, int(overlap), int(image_hw[0]), int(image_hw[1]), _p(out), _p(pt),
+                               _p(scales), _stream())
+    _check(rc, "vggt_pose_align")
+    return out, pt, scales
 
 
 def scale_(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:

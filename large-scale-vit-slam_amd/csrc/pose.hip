@@ -263,7 +263,253 @@ __global__ __launch_bounds__(64) void pose_compose_kernel(
   }
 }
 
+// top_eigvec4 with the winning column picked by selects: its V[k][b] with a run-time b
+// puts V into scratch (144 B per lane in pose_compose_kernel, whose code stays as it is).
+// The sweeps are top_eigvec4's, operation for operation: keep the two bodies in step.
+__device__ void top_eigvec4_sel(const double Min[4][4], double* v) {
+  double A[4][4], V[4][4];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      A[i][j] = Min[i][j];
+      V[i][j] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < 4; ++p)
+      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
+    if (off < 1e-60) break;
+    for (int p = 0; p < 3; ++p)
+      for (int q = p + 1; q < 4; ++q) {
+        if (fabs(A[p][q]) < 1e-300) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 4; ++k) {  // A <- J^T A J
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int b = 0;
+  double best = A[0][0];
+  for (int i = 1; i < 4; ++i)
+    if (A[i][i] > best) { best = A[i][i]; b = i; }
+  double col[4];
+  for (int k = 0; k < 4; ++k) col[k] = b == 0 ? V[k][0] : b == 1 ? V[k][1] : b == 2 ? V[k][2] : V[k][3];
+  double n = 0.0;
+  for (int k = 0; k < 4; ++k) n += col[k] * col[k];
+  n = sqrt(n);
+  for (int k = 0; k < 4; ++k) v[k] = col[k] / n;
+}
+
+// Per-chunk pose algebra of the pose-aligned VGGT (poseAligned_wrapped_vggt.py:74-130,
+// 172-177) as one launch: re-centring on the first frame, the GT scale of the
+// translations (:84-104, scale_lse_solver), the mean transform (identity | GT first
+// pose | Markley mean over the overlap), the aligned encoding and the point transform.
+// Same layout as pose_compose_kernel: one 64-lane workgroup per batch element, lane-stride
+// over frames.  The GT scale |sum x.y / sum x^2| is taken in fp64 from the raw encodings
+// (per-lane partials, combined by lane 0 in lane order: no atomics, independent of the
+// grid), the quotient rounded to fp32 once; everything else is fp32 as the reference's, the
+// translations take one fp32 multiply.
+__global__ __launch_bounds__(64) void pose_align_kernel(
+    const float* __restrict__ cam, const float* __restrict__ ctx, int S_prev, const float* __restrict__ gt, int S,
+    int ov, float H, float W, float* __restrict__ out, float* __restrict__ pt_out, float* __restrict__ scales) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  __shared__ Aff s_ident, s_mean, s_ptid;
+  __shared__ float s_scale;
+  __shared__ double s_part[64][2];
+  __shared__ float s_ct[MAX_OV][7];  // overlap transforms as [t, quat] (Markley input)
+  const float* cb = cam + (int64_t)b * S * 9;
+  const float* gb = gt != nullptr ? gt + (int64_t)b * S * 12 : nullptr;
+  auto gt_aff = [&](int f) {  // gt_poses[b, f] (3 x 4, row-major)
+    const float* g = gb + (int64_t)f * 12;
+    Aff m;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) m.r[i][j] = g[i * 4 + j];
+      m.t[i] = g[i * 4 + 3];
+    }
+    return m;
+  };
+  if (lane == 0) {
+    // pose_encoding_to_extri_intri (VGGT): quat_to_mat on the raw quaternion
+    Aff e0;
+    quat_to_mat(cb + 3, e0.r);
+    e0.t[0] = cb[0]; e0.t[1] = cb[1]; e0.t[2] = cb[2];
+    s_ptid = e0;               // point_identity_alignment, :80
+    s_ident = inv_se3(e0);     // :79
+  }
+  __syncthreads();
+  // camera extrinsics of frame f re-centred on frame 0 (:81), translation not yet scaled.  Frame 0
+  // takes lane 0's matrix: a second evaluation of quat_to_mat may be contracted differently, and
+  // R0 R0^T is symmetric (an exact identity quaternion, as the reference's) only for one R0.
+  auto extr = [&](int f) {
+    if (f == 0) return mul(s_ptid, s_ident);
+    const float* c = cb + (int64_t)f * 9;
+    Aff e;
+    quat_to_mat(c + 3, e.r);
+    e.t[0] = c[0]; e.t[1] = c[1]; e.t[2] = c[2];
+    return mul(e, s_ident);
+  };
+  if (gb != nullptr) {  // :92-104
+    // The operands of the scale in fp64 from the raw encodings: the re-centring cancels
+    // (x_f = R_f (-R0^T t0) + t_f), and taken in fp32 its rounding, not that of the sums, decides
+    // how far the scale is from the exact one (up to 2 x the fp32 restatement's error).
+    auto rot64 = [](const float* q, double R[3][3]) {  // quat_to_mat in fp64
+      const double i = q[0], j = q[1], k = q[2], r = q[3];
+      const double two_s = 2.0 / (i * i + j * j + k * k + r * r);
+      R[0][0] = 1.0 - two_s * (j * j + k * k); R[0][1] = two_s * (i * j - k * r); R[0][2] = two_s * (i * k + j * r);
+      R[1][0] = two_s * (i * j + k * r); R[1][1] = 1.0 - two_s * (i * i + k * k); R[1][2] = two_s * (j * k - i * r);
+      R[2][0] = two_s * (i * k - j * r); R[2][1] = two_s * (j * k + i * r); R[2][2] = 1.0 - two_s * (i * i + j * j);
+    };
+    double R0[3][3], tinv[3], ginv[3];  // the translations of inv(extr[0]) and inv(gt[0])
+    rot64(cb + 3, R0);
+    for (int i = 0; i < 3; ++i) {
+      tinv[i] = -(R0[0][i] * (double)cb[0] + R0[1][i] * (double)cb[1] + R0[2][i] * (double)cb[2]);
+      ginv[i] = -((double)gb[i] * (double)gb[3] + (double)gb[4 + i] * (double)gb[7] + (double)gb[8 + i] * (double)gb[11]);
+    }
+    double sxy = 0.0, sxx = 0.0;
+    for (int f = lane; f < S; f += 64) {
+      const float* c = cb + (int64_t)f * 9;
+      const float* g = gb + (int64_t)f * 12;
+      double R[3][3];
+      rot64(c + 3, R);
+      for (int i = 0; i < 3; ++i) {
+        const double x = R[i][0] * tinv[0] + R[i][1] * tinv[1] + R[i][2] * tinv[2] + (double)c[i];
+        const double y = (double)g[i * 4] * ginv[0] + (double)g[i * 4 + 1] * ginv[1] + (double)g[i * 4 + 2] * ginv[2]
+                         + (double)g[i * 4 + 3];
+        sxy += x * y;
+        sxx += x * x;
+      }
+    }
+    s_part[lane][0] = sxy;
+    s_part[lane][1] = sxx;
+    __syncthreads();
+    if (lane == 0) {
+      double a = 0.0, d = 0.0;
+      for (int k = 0; k < 64; ++k) {
+        a += s_part[k][0];
+        d += s_part[k][1];
+      }
+      s_scale = fabsf((float)(a / d));  // 0 / 0: NaN, kept
+    }
+  } else if (lane == 0) {
+    s_scale = 1.0f;
+  }
+  // mean transform (:107-126)
+  if (ctx == nullptr) {
+    if (lane == 0) {
+      Aff I;
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) I.r[i][j] = i == j ? 1.f : 0.f;
+        I.t[i] = 0.f;
+      }
+      s_mean = I;
+    }
+  } else if (gb != nullptr) {
+    if (lane == 0) s_mean = gt_aff(0);  // gt_poses[:, :1], not centred (:109)
+  } else {
+    const float* cx = ctx + (int64_t)b * S_prev * 9;
+    for (int k = lane; k < ov; k += 64) {
+      const Aff co = enc_to_aff(cx + (int64_t)(S_prev - ov + k) * 9);  // context pose_enc[-1][:, -ov:], :111
+      const Aff ct = mul(inv_se3(extr(k)), co);                      // :113-115
+      if (ov == 1) {
+        s_mean = ct;                                                   // :124
+      } else {                                                         // extri_to_pose_encoding (data.py:12-30)
+        float q[4];
+        mat_to_quat(ct.r, q);
+        normalize4(q);
+        s_ct[k][0] = ct.t[0]; s_ct[k][1] = ct.t[1]; s_ct[k][2] = ct.t[2];
+        for (int i = 0; i < 4; ++i) s_ct[k][3 + i] = q[i];
+      }
+    }
+    __syncthreads();
+    if (ov > 1 && lane == 0) {  // averagePoseEncodings (geometry.py:4-37)
+      float t[3] = {0.f, 0.f, 0.f};
+      for (int k = 0; k < ov; ++k)
+        for (int i = 0; i < 3; ++i) t[i] += s_ct[k][i];
+      const float inv_n = 1.0f / (float)ov;
+      float M[4][4] = {};
+      for (int k = 0; k < ov; ++k) {
+        float q[4] = {s_ct[k][3], s_ct[k][4], s_ct[k][5], s_ct[k][6]};
+        normalize4(q);
+        for (int i = 0; i < 4; ++i)
+          for (int j = 0; j < 4; ++j) M[i][j] += inv_n * (q[i] * q[j]);
+      }
+      double Md[4][4], v[4];
+      for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) Md[i][j] = M[i][j];
+      top_eigvec4_sel(Md, v);
+      float e[7] = {t[0] / (float)ov, t[1] / (float)ov, t[2] / (float)ov, (float)v[0], (float)v[1], (float)v[2],
+                    (float)v[3]};
+      s_mean = enc_to_aff(e);  // pose_encoding_to_extri(mean), :122
+    }
+  }
+  __syncthreads();
+  const float scale = s_scale;
+  if (lane == 0) {
+    scales[b] = scale;
+    if (pt_out != nullptr) {
+      // point transform (:171-177): context ? inv(mean) @ ptid : ptid
+      const Aff p = ctx != nullptr ? mul(inv_se3(s_mean), s_ptid) : s_ptid;
+      float* po = pt_out + (int64_t)b * 16;
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) po[i * 4 + j] = p.r[i][j];
+        po[i * 4 + 3] = p.t[i];
+      }
+      po[12] = 0.f; po[13] = 0.f; po[14] = 0.f; po[15] = 1.f;
+    }
+  }
+  // scaled extrinsics composed with the mean transform (:129), encoded with the camera FoV (:130)
+  for (int f = lane; f < S; f += 64) {
+    Aff e = extr(f);
+    for (int i = 0; i < 3; ++i) e.t[i] *= scale;  // :102
+    Aff a = mul(e, s_mean);
+    // the reference's 4 x 4 product adds extr[i][3] * mean[3][j] = t_i * 0 to the rotation: +0 for a
+    // finite translation, NaN under a NaN scale (0 / 0) -- the quaternion is NaN there too
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) a.r[i][j] += e.t[i] * 0.f;
+    float q[4];
+    mat_to_quat(a.r, q);
+    const float* c = cb + (int64_t)f * 9;
+    // the FoV round trip in fp64, rounded once (as pose_compose_kernel)
+    const double fy = ((double)H / 2.0) / tan((double)c[7] / 2.0);
+    const double fx = ((double)W / 2.0) / tan((double)c[8] / 2.0);
+    float* o = out + ((int64_t)b * S + f) * 9;
+    o[0] = a.t[0]; o[1] = a.t[1]; o[2] = a.t[2];
+    o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+    o[7] = (float)(2.0 * atan(((double)H / 2.0) / fy));
+    o[8] = (float)(2.0 * atan(((double)W / 2.0) / fx));
+  }
+}
+
 }  // namespace
+
+extern "C" int vggt_pose_align(const float* cam_pose_enc, const float* ctx_pose_enc, int S_prev, const float* gt,
+                               int B, int S, int overlap, int H, int W, float* aligned_pose_enc,
+                               float* point_transform, float* scales, void* stream) {
+  if (B <= 0 || S <= 0 || H <= 0 || W <= 0) return VGGT_ERR_SHAPE;
+  if (!cam_pose_enc || !aligned_pose_enc || !scales) return VGGT_ERR_SHAPE;
+  if (gt != nullptr && S == 1) return VGGT_ERR_SHAPE;  // the reference defines no scale for one frame
+  if (ctx_pose_enc != nullptr && gt == nullptr) {
+    if (overlap < 1 || overlap > S || overlap > S_prev || overlap > MAX_OV) return VGGT_ERR_SHAPE;
+  }
+  pose_align_kernel<<<B, 64, 0, (hipStream_t)stream>>>(cam_pose_enc, ctx_pose_enc, S_prev, gt, S, overlap, (float)H,
+                                                       (float)W, aligned_pose_enc, point_transform, scales);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
 
 extern "C" int vggt_pose_compose(const float* chunk_sim3, const float* frame_se3, const float* cam_pose_enc,
                                  const float* ctx_pose_enc, int S_prev, const float* gt_first, int B, int S,
