@@ -838,6 +838,66 @@ int vggt_pose_align(const float* cam_pose_enc, const float* ctx_pose_enc, int S_
                     int overlap, int H, int W, float* aligned_pose_enc, float* point_transform, float* scales,
                     void* stream);
 
+/*
+ * GT alignment of a merged sequence from its poses (aligned_vggt/utils/alignment.py
+ * of the reference: :206-242, :131-165, :325-370 with :6-59), one launch, one
+ * 64-lane workgroup per batch element, lane-strided over frames.  Sums are
+ * per-lane fp64 partials combined in lane order (no atomics, results independent
+ * of the grid); every result is an fp64 function of the fp32 inputs rounded once.
+ * pose_enc [B,S,enc_width] (enc_width 7 or 9: T, quat xyzw[, FoV h/w]), gt_extr
+ * [B,S,3,4] w2c; fp32 contiguous device.  W = -1 means S, else 1 <= W <= S.
+ *   VGGT_GT_POSE_SCALE      scales[b] = |sum x.y / sum x.x| over x = pose_enc[b,:W,:3],
+ *                           y = gt_extr[b,:W,:3,3]  (scales [B])
+ *   VGGT_GT_POSE_PER_FRAME  scales[b,0] = 1, scales[b,f] the same quotient over frame f
+ *                           alone (scales [B,S]; W is not used)
+ *   VGGT_GT_POSE_SIM3       Umeyama x -> y over the first W camera centres -R^T t (x from
+ *                           pose_enc with the raw quaternion, y from gt_extr): means,
+ *                           sigma_x and the covariance in fp64, the 3x3 SVD by Jacobi on
+ *                           C^T C, the det(u) det(v) < 0 reflection fix.  transform [B,4,4]
+ *                           = [R | t; 0 0 0 1], scales [B] = c.  With pose_enc_out
+ *                           [B,S,9] non-NULL also the aligned encoding of all S frames
+ *                           (fp32 as the reference: w2c -> c2w, translation x c,
+ *                           transform ., -> w2c, mat_to_quat; FoV through the focal
+ *                           length and back in fp64 for an img_h x img_w image);
+ *                           pose_enc_out may be pose_enc.  Needs W >= 3 centres that are
+ *                           not collinear: with fewer, or collinear ones, the rotation
+ *                           about their line is not determined and sigma_x == 0 gives a
+ *                           non-finite scale, as the reference's 1 / sigma_x.
+ * A quotient that is 0/0 in the reference is NaN here.  transform and pose_enc_out
+ * are neither read nor written in the first two modes.
+ * VGGT_ERR_SHAPE: non-positive B or S, a NULL pose_enc / gt_extr / scales, enc_width
+ * not 7 or 9, W outside [1, S], SIM3 without transform or with pose_enc_out and a
+ * non-positive image size.  VGGT_ERR_UNSUPPORTED: an unknown mode; SIM3 with
+ * enc_width 7 (the reference fails there too).
+ */
+#define VGGT_GT_POSE_SCALE 0
+#define VGGT_GT_POSE_PER_FRAME 1
+#define VGGT_GT_POSE_SIM3 2
+int vggt_gt_pose_align(const float* pose_enc, int enc_width, const float* gt_extr, int B, int S, int W, int mode,
+                       int img_h, int img_w, float* scales, float* transform, float* pose_enc_out, void* stream);
+
+/*
+ * The per-frame terms of one ATE / RPE / ScaleConsistency update
+ * (eval/trajectory_metrics.py of the reference: :28-48, :154-182, :306-331) for B
+ * sequences in one launch, one 64-lane workgroup per sequence.  pred_c2w, gt_c2w
+ * [B,S,4,4] fp32 contiguous device.  Any output may be NULL:
+ *   ate_vec [B,S,3]      pred[:3,3] - gt[:3,3]
+ *   ate_norm [B,S]       its Euclidean norm
+ *   rpe_trans, rpe_rot [B,S-delta]  for the pairs (i, i + delta), with
+ *                        err = inv(inv(g_i) g_j) . inv(p_i) p_j: |err[:3,3]| and
+ *                        acos(clamp((tr(err[:3,:3]) - 1) / 2, -1, 1)) in radians;
+ *                        S <= delta writes nothing to either
+ *   scale_factor [B,S-1] for the frames 1..S-1, g.p / max(p.p, 1e-8f) over the
+ *                        translations p of pred and g of gt
+ * inv is the general 4x4 inverse (adjugate), not the rigid closed form, as
+ * torch.linalg.inv in the reference.  Everything is computed in fp64 from the
+ * fp32 inputs and rounded once.  A singular pose gives non-finite outputs where
+ * the reference raises.  VGGT_ERR_SHAPE: non-positive B or S, delta < 1, a NULL
+ * input.
+ */
+int vggt_trajectory_errors(const float* pred_c2w, const float* gt_c2w, int B, int S, int delta, float* ate_vec,
+                           float* ate_norm, float* rpe_trans, float* rpe_rot, float* scale_factor, void* stream);
+
 /* ======================================================================
  * Training (backward) entry points -- alignment-head training, SURVEY.md §8f
  * row 4: train_featureAlignedVGGT_vkitti.yaml freezes the aggregator, camera

@@ -131,6 +131,9 @@ _SIGS = {
     "vggt_depth_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     # GT scale alignment (csrc/gt_align.hip)
     "vggt_depth_scale_l1": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    # GT alignment from poses and the trajectory-metric terms (csrc/pose.hip)
+    "vggt_gt_pose_align": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "vggt_trajectory_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspace_bytes": [_i, _i],
            "vggt_headnorm_rope_bwd_workspace_bytes": [_i, _i], "vggt_batch_dot_workspace_bytes": [_i, _i64],
@@ -946,6 +949,70 @@ def pose_align(cam_pose_enc: torch.Tensor, ctx_pose_enc: Optional[torch.Tensor],
                                _p(scales), _stream())
     _check(rc, "vggt_pose_align")
     return out, pt, scales
+
+
+GT_POSE_SCALE, GT_POSE_PER_FRAME, GT_POSE_SIM3 = 0, 1, 2
+
+
+def gt_pose_align(pose_enc: torch.Tensor, gt_extr: torch.Tensor, mode: int, seq_width: int = -1, image_hw=None,
+                  pose_enc_out: Optional[torch.Tensor] = None):
+    """vggt_gt_pose_align on the current stream -> (scales, transform, pose_enc_out).
+    pose_enc (B,S,7|9) and gt_extr (B,S,3,4) w2c: contiguous fp32 on one device.
+    scales is (B,) -- (B,S) for GT_POSE_PER_FRAME --, transform (B,4,4) for GT_POSE_SIM3
+    (None otherwise).  GT_POSE_SIM3 with ``image_hw`` also writes the aligned encoding of
+    all S frames into ``pose_enc_out`` (a new tensor unless one is given; it may be
+    ``pose_enc`` itself)."""
+    _dev(pose_enc, "gt_pose_align")
+    dev = pose_enc.device
+    assert pose_enc.dim() == 3 and pose_enc.shape[2] in (7, 9), "gt_pose_align: pose_enc (B, S, 7 | 9)"
+    B, S, ew = pose_enc.shape
+    assert gt_extr.shape == (B, S, 3, 4), "gt_pose_align: gt_extr (B, S, 3, 4)"
+    for t in (pose_enc, gt_extr, pose_enc_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev), \
+            "gt_pose_align: contiguous fp32 tensors on one device"
+    scales = torch.empty((B, S) if mode == GT_POSE_PER_FRAME else (B,), device=dev, dtype=torch.float32)
+    transform = torch.empty(B, 4, 4, device=dev, dtype=torch.float32) if mode == GT_POSE_SIM3 else None
+    H = W = 0
+    if mode == GT_POSE_SIM3 and ew == 9 and image_hw is not None:
+        H, W = int(image_hw[0]), int(image_hw[1])
+        if pose_enc_out is None:
+            pose_enc_out = torch.empty(B, S, 9, device=dev, dtype=torch.float32)
+        assert pose_enc_out.shape == (B, S, 9)
+    else:
+        pose_enc_out = None
+    rc = lib().vggt_gt_pose_align(_p(pose_enc), ew, _p(gt_extr), B, S, int(seq_width), int(mode), H, W, _p(scales),
+                                  _p(transform), _p(pose_enc_out), _stream())
+    _check(rc, "vggt_gt_pose_align")
+    return scales, transform, pose_enc_out
+
+
+def trajectory_errors(pred_c2w: torch.Tensor, gt_c2w: torch.Tensor, delta: int = 1, ate: bool = True,
+                      rpe: bool = True, scale: bool = True) -> dict:
+    """vggt_trajectory_errors on the current stream.  pred_c2w, gt_c2w (B,S,4,4)
+    contiguous fp32 on one device -> dict with the outputs asked for: ``ate_vec``
+    (B,S,3), ``ate_norm`` (B,S), ``rpe_trans`` / ``rpe_rot`` (B,max(S-delta,0)) and
+    ``scale_factor`` (B,S-1)."""
+    _dev(pred_c2w, "trajectory_errors")
+    dev = pred_c2w.device
+    assert pred_c2w.dim() == 4 and pred_c2w.shape[2:] == (4, 4) and gt_c2w.shape == pred_c2w.shape, \
+        "trajectory_errors: (B, S, 4, 4) poses of one shape"
+    for t in (pred_c2w, gt_c2w):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == dev, \
+            "trajectory_errors: contiguous fp32 tensors on one device"
+    B, S = pred_c2w.shape[:2]
+    new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+    out = {}
+    if ate:
+        out["ate_vec"], out["ate_norm"] = new(B, S, 3), new(B, S)
+    if rpe:
+        out["rpe_trans"], out["rpe_rot"] = new(B, max(S - delta, 0)), new(B, max(S - delta, 0))
+    if scale:
+        out["scale_factor"] = new(B, S - 1)
+    rc = lib().vggt_trajectory_errors(_p(pred_c2w), _p(gt_c2w), B, S, int(delta), _p(out.get("ate_vec")),
+                                      _p(out.get("ate_norm")), _p(out.get("rpe_trans")), _p(out.get("rpe_rot")),
+                                      _p(out.get("scale_factor")), _stream())
+    _check(rc, "vggt_trajectory_errors")
+    return out
 
 
 def scale_(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:

@@ -112,6 +112,48 @@ class ChamferDistanceMetrics:
         comp = self.gt_to_pred.mean().item() if len(self.gt_to_pred) > 0 else 0.0
         return {"chamfer_distance": 0.5 * acc + 0.5 * comp, "accuracy": acc, "completion": comp}
 
+    def to(self, target):
+        """Move the accumulated distances to a device, or to the device of a tensor (as
+        the reference's ``metric.to(gt_points[0])``); returns self.  With the state on
+        the clouds' device ``update`` copies nothing to the host."""
+        device = target.device if isinstance(target, torch.Tensor) else torch.device(target)
+        self.pred_to_gt, self.gt_to_pred = self.pred_to_gt.to(device), self.gt_to_pred.to(device)
+        return self
+
+    def plot(self, preds: torch.Tensor, target: torch.Tensor, title: Optional[str] = None,
+             outpath: Optional[str] = None) -> Tuple[dict, str]:
+        """reconstruction_metrics.py:86-153: the metric of one pair of clouds ((N_pred, 3),
+        (N_gt, 3)) and the histogram of both distance vectors;
+        ``{outpath}rec_chamfer_distribution.png`` / ``.npy`` are written only with
+        ``outpath``.  Returns ``(dict, path)`` with ``compute()``'s keys and types: 0-dim
+        tensors under ``rmse=True``, Python floats otherwise."""
+        import numpy as np
+        from .trajectory_metrics import _new_figure, _write_plot
+
+        def reduce(d):  # one direction's figure of merit
+            if len(d) == 0:
+                return 0.0
+            return torch.sqrt((d ** 2).mean()) if self.rmse else d.mean().item()
+        dists = dict(zip(("pred_to_gt", "gt_to_pred"), self.distances(preds, target)))
+        acc, comp = reduce(dists["pred_to_gt"]), reduce(dists["gt_to_pred"])
+        names = ("chamfer_distance", "accuracy", "completion")
+        values = (0.5 * acc + 0.5 * comp, acc, comp)
+        result = {n + ("_rmse" if self.rmse else ""): v for n, v in zip(names, values)}
+        host = {k: d.cpu().numpy() for k, d in dists.items()}
+        fig, ax = _new_figure((6, 6), title)
+        for key, label in (("pred_to_gt", "Pred\u2192GT"), ("gt_to_pred", "GT\u2192Pred")):
+            ax.hist(host[key], bins=100, alpha=0.5, label=label)
+        ax.set_xlabel("Distance")
+        ax.set_ylabel("Count")
+        ax.legend()
+        unit = " RMSE" if self.rmse else ""
+        ax.set_title(", ".join("%s%s: %.3f m" % (what, unit, float(v))
+                               for what, v in zip(("Chamfer", "Accuracy", "Completion"), values)), fontsize=10)
+        data = {"dists_" + k: v for k, v in host.items()}
+        data.update((k, np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v))
+                    for k, v in zip(("chamfer", "acc", "comp"), values))
+        return result, _write_plot(fig, outpath, "rec_chamfer_distribution", data)
+
     __call__ = update
 
 

@@ -12,7 +12,16 @@ Two kinds of callers:
   * a training step with ``gt_alignment_type: scale_from_depths`` runs
     ``scale_align_from_depths`` on the step's device tensors, between the model
     and the loss: there the weighted median is the HIP kernel
-    ``vggt_depth_scale_l1`` (csrc/gt_align.hip) and nothing visits the host.
+    ``vggt_depth_scale_l1`` (csrc/gt_align.hip) and nothing visits the host;
+  * the five pose-based GT alignments (``scale_from_poses``, ``scale_from_fc_poses``,
+    ``per_frame_scale_from_poses``, ``per_chunk_scale_from_poses``,
+    ``sim3_from_poses``) take the kernel ``vggt_gt_pose_align`` (csrc/pose.hip)
+    when the pose encoding and the GT extrinsics are fp32 tensors on one HIP
+    device: the scale / transform stays on the device and nothing synchronises.
+    Host tensors, other dtypes and VGGT_GT_ALIGN=torch run the reference's host
+    code.  ``sim3_from_points`` stays on the host: its ``reshape(3, -1)`` of an
+    (n, 3) selection is not the transpose a kernel would compute, and it runs
+    once per evaluated sequence.
 """
 from __future__ import annotations
 
@@ -75,6 +84,8 @@ def scale_lse_solver(x: np.ndarray, y: np.ndarray) -> float:
 def per_frame_scale_alignment_from_poses(predictions: dict, batch: dict) -> None:
     """alignment.py:131-165 (note: ``alignment_scales`` keeps the last batch
     element's per-frame list, as the reference does)."""
+    if _pose_align_kernel_applies(predictions["pose_enc"], batch["extrinsics"]):
+        return _per_frame_scale_alignment_from_poses_device(predictions, batch)
     B, S = batch["extrinsics"].shape[:2]
     gt_positions = batch["extrinsics"][..., :3, 3].detach().cpu().numpy()
     pred_positions = predictions["pose_enc"][..., :3].detach().cpu().numpy()
@@ -94,6 +105,8 @@ def per_frame_scale_alignment_from_poses(predictions: dict, batch: dict) -> None
 
 def per_chunk_scale_alignment_from_poses(predictions: dict, batch: dict) -> None:
     """alignment.py:167-204 (chunked lists)."""
+    if all(_pose_align_kernel_applies(p, e) for p, e in zip(predictions["pose_enc"], batch["extrinsics"])):
+        return _per_chunk_scale_alignment_from_poses_device(predictions, batch)
     C = len(batch["extrinsics"])
     B = batch["extrinsics"][0].shape[0]
     chunk_scales = []
@@ -116,6 +129,8 @@ def per_chunk_scale_alignment_from_poses(predictions: dict, batch: dict) -> None
 
 def scale_alignment_from_poses(predictions: dict, batch: dict, seq_width: int = -1) -> None:
     """alignment.py:206-242."""
+    if _pose_align_kernel_applies(predictions["pose_enc"], batch["extrinsics"]):
+        return _scale_alignment_from_poses_device(predictions, batch, seq_width)
     B = batch["extrinsics"].shape[0]
     if seq_width == -1:
         seq_width = batch["extrinsics"].shape[1]
@@ -131,6 +146,73 @@ def scale_alignment_from_poses(predictions: dict, batch: dict, seq_width: int = 
         if "world_points" in predictions:
             predictions["world_points"][b, ...] *= sc
     predictions["alignment_scales"] = scales
+
+
+def _pose_align_kernel_applies(pose_enc, extrinsics) -> bool:
+    """Pose encoding and GT extrinsics fp32 on one HIP device; VGGT_GT_ALIGN=torch (read
+    per call) keeps the host code."""
+    if os.environ.get("VGGT_GT_ALIGN", "") == "torch":
+        return False
+    return (torch.is_tensor(pose_enc) and torch.is_tensor(extrinsics) and pose_enc.is_cuda
+            and extrinsics.device == pose_enc.device and pose_enc.dtype == torch.float32
+            and extrinsics.dtype == torch.float32)
+
+
+def _pose_align_launch(pose_enc, extrinsics, mode, seq_width=-1, image_hw=None):
+    """vggt_gt_pose_align on detached contiguous views: (scales, transform, pose_enc_out)."""
+    from .. import _native
+    with torch.no_grad():
+        return _native.gt_pose_align(pose_enc.detach().contiguous(), extrinsics.detach()[..., :3, :].contiguous(),
+                                     mode, seq_width, image_hw)
+
+
+def _scale_alignment_from_poses_device(predictions: dict, batch: dict, seq_width: int) -> None:
+    """The kernel route of scale_alignment_from_poses: the LSE scale from device memory,
+    no host synchronisation; ``alignment_scales`` is a list of 0-dim device tensors."""
+    from .. import _native
+    S = batch["extrinsics"].shape[1]
+    W = -1 if seq_width == -1 else min(int(seq_width), S)  # a slice past the end stops at S
+    scales, _, _ = _pose_align_launch(predictions["pose_enc"], batch["extrinsics"], _native.GT_POSE_SCALE, W)
+    predictions["pose_enc"][..., :3] *= scales[:, None, None]  # torch's in-place multiply: autograd records it
+    if "depth" in predictions:
+        _scale_batch_(predictions["depth"], scales)
+    if "world_points" in predictions:
+        _scale_batch_(predictions["world_points"], scales)
+    predictions["alignment_scales"] = list(scales.unbind(0))
+
+
+def _per_frame_scale_alignment_from_poses_device(predictions: dict, batch: dict) -> None:
+    """The kernel route of per_frame_scale_alignment_from_poses; dense tensors are scaled
+    as B * S blocks.  ``alignment_scales``: the last batch element's S values, as the
+    reference keeps them, here 0-dim device tensors."""
+    from .. import _native
+    B, S = batch["extrinsics"].shape[:2]
+    scales, _, _ = _pose_align_launch(predictions["pose_enc"], batch["extrinsics"], _native.GT_POSE_PER_FRAME)
+    predictions["pose_enc"][..., :3] *= scales[:, :, None]
+    for key in ("depth", "world_points"):
+        if key in predictions:
+            t = predictions[key]
+            if t.is_contiguous():
+                _scale_batch_(t.view(B * S, *t.shape[2:]), scales.view(B * S))
+            else:
+                t *= scales.view(B, S, *([1] * (t.dim() - 2)))
+    predictions["alignment_scales"] = list(scales[-1].unbind(0))
+
+
+def _per_chunk_scale_alignment_from_poses_device(predictions: dict, batch: dict) -> None:
+    """The kernel route of per_chunk_scale_alignment_from_poses: one launch per chunk;
+    ``alignment_scales_per_chunk`` is a list of (B,) device tensors."""
+    from .. import _native
+    chunk_scales = []
+    for c in range(len(batch["extrinsics"])):
+        scales, _, _ = _pose_align_launch(predictions["pose_enc"][c], batch["extrinsics"][c], _native.GT_POSE_SCALE)
+        predictions["pose_enc"][c][..., :3] *= scales[:, None, None]
+        if "depth" in predictions:
+            _scale_batch_(predictions["depth"][c], scales)
+        if "world_points" in predictions:
+            _scale_batch_(predictions["world_points"][c], scales)
+        chunk_scales.append(scales)
+    predictions["alignment_scales_per_chunk"] = chunk_scales
 
 
 def _gt_align_kernel_applies(d_pred, conf, d_gt, mask) -> bool:
@@ -271,11 +353,17 @@ def apply_sim3_alignment_on_w2c(extr: torch.Tensor, alignment_transform: torch.T
 
 def apply_sim3_alignment(alignment_transforms, alignment_scales, pose_encodings, images_size, points=None,
                          depths=None) -> tuple:
-    """alignment.py:449-489."""
+    """alignment.py:449-489.  Transforms and scales may be arrays (the reference's) or
+    tensors, which stay where they are when that is the encodings' device."""
     B = alignment_transforms.shape[0]
     dev = pose_encodings.device
-    sc = torch.as_tensor(np.asarray(alignment_scales), dtype=torch.float32, device=dev)
-    T = torch.as_tensor(np.asarray(alignment_transforms), dtype=torch.float32, device=dev)
+
+    def f32(a):
+        if isinstance(a, torch.Tensor):
+            return a.to(device=dev, dtype=torch.float32)
+        return torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev)
+    sc = f32(alignment_scales)
+    T = f32(alignment_transforms)
     extr, intr = pose_encoding_to_extri_intri(pose_encodings, images_size)
     extr = apply_sim3_alignment_on_w2c(extr, T, sc)
     pose_encodings = extri_intri_to_pose_encoding(extr, intr, images_size)
@@ -299,6 +387,8 @@ def apply_sim3_alignment_on_dict(pred: dict, images_size: tuple, alignment_poses
 
 def umeyama_alignment_from_poses(predictions: dict, batch: dict, seq_width: int) -> None:
     """alignment.py:325-370: Sim(3) of predicted to GT camera centres."""
+    if _pose_align_kernel_applies(predictions["pose_enc"], batch["extrinsics"]):
+        return _umeyama_alignment_from_poses_device(predictions, batch, seq_width)
     B = batch["extrinsics"].shape[0]
     gt_poses = closed_form_inverse_se3(batch["extrinsics"][:, :seq_width].reshape(B * seq_width, 3, 4)).reshape(
         B, seq_width, 4, 4).detach().cpu().numpy()
@@ -318,6 +408,34 @@ def umeyama_alignment_from_poses(predictions: dict, batch: dict, seq_width: int)
                                       batch["images"].shape[-2:], predictions.get("world_points"),
                                       predictions.get("depth"))
     predictions["pose_enc"] = pe
+    if "world_points" in predictions:
+        predictions["world_points"] = pts
+    if "depth" in predictions:
+        predictions["depth"] = d
+
+
+def _umeyama_alignment_from_poses_device(predictions: dict, batch: dict, seq_width: int) -> None:
+    """The kernel route of umeyama_alignment_from_poses: transform and scale stay on the
+    device.  When nothing requires grad the kernel also writes the aligned encoding and
+    the dense tensors take vggt_sim3_points / the scale kernel; otherwise
+    apply_sim3_alignment's differentiable torch chain runs with the device transform."""
+    from .. import _native
+    image_hw = batch["images"].shape[-2:]
+    tracked = torch.is_grad_enabled() and any(
+        predictions[k].requires_grad for k in ("pose_enc", "world_points", "depth") if k in predictions)
+    scales, T, enc = _pose_align_launch(predictions["pose_enc"], batch["extrinsics"], _native.GT_POSE_SIM3,
+                                        int(seq_width), None if tracked else image_hw)
+    if tracked:
+        enc, pts, d = apply_sim3_alignment(T, scales, predictions["pose_enc"], image_hw,
+                                           predictions.get("world_points"), predictions.get("depth"))
+    else:
+        pts = d = None
+        if "world_points" in predictions:
+            pts = apply_sim3_alignment_on_point_maps(predictions["world_points"], T, scales)
+        if "depth" in predictions:
+            d = predictions["depth"]
+            _scale_batch_(d, scales)
+    predictions["pose_enc"] = enc
     if "world_points" in predictions:
         predictions["world_points"] = pts
     if "depth" in predictions:

@@ -1,8 +1,11 @@
-"""Chunking and pose-encoding glue (aligned_vggt/utils/data.py:12-225)."""
+"""Chunking, pose-encoding and GT-normalisation glue (aligned_vggt/utils/data.py:12-335)."""
 from __future__ import annotations
 
+import contextlib
+import contextvars
+import logging
 import random
-from typing import Optional, List
+from typing import Optional, List, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -78,10 +81,29 @@ def _side_stream(device) -> "torch.cuda.Stream":
     return s
 
 
+_KEEP_CHUNK_OUTPUTS = contextvars.ContextVar("aligned_vggt_keep_chunk_outputs", default=False)
+
+
+@contextlib.contextmanager
+def chunk_outputs_stay_in_place():
+    """Within this context (of the calling thread or task) ``moveDictListItemToCPU``
+    copies nothing: a sequence driver that offloads older chunk outputs through it
+    leaves them where the model produced them, so its merge and its GT alignment run
+    on the device.  That holds every chunk's outputs in device memory until the merge."""
+    token = _KEEP_CHUNK_OUTPUTS.set(True)
+    try:
+        yield
+    finally:
+        _KEEP_CHUNK_OUTPUTS.reset(token)
+
+
 def moveDictListItemToCPU(chunked_dict: dict, itemIndex: int, pending: Optional[list] = None) -> None:
     """data.py:89-106.  ``pending`` (a list): the copies run asynchronously into
     pinned host tensors and their completion events are appended -- the caller
-    must wait on them (``wait_host_copies``) before reading the host tensors."""
+    must wait on them (``wait_host_copies``) before reading the host tensors.
+    A no-op inside ``chunk_outputs_stay_in_place()``."""
+    if _KEEP_CHUNK_OUTPUTS.get():
+        return
     for key in chunked_dict.keys():
         v = chunked_dict[key]
         if isinstance(v, list) and len(v) >= (abs(itemIndex) if itemIndex < 0 else itemIndex + 1):
@@ -172,3 +194,54 @@ def chunk_batch(batch: dict, indices: list) -> dict:
             if isinstance(batch[key], torch.Tensor):
                 out.setdefault(key, []).append(batch[key][:, ids])
     return out
+
+
+def check_valid_tensor(input_tensor: Optional[torch.Tensor], name: str = "tensor") -> None:
+    """data.py:228-238: log a warning when a tensor holds NaN or Inf."""
+    if input_tensor is not None and not bool(torch.isfinite(input_tensor).all()):
+        logging.warning(f"NaN or Inf found in tensor: {name}")
+
+
+def normalize_camera_extrinsics_and_points_batch(
+        extrinsics: torch.Tensor, cam_points: Optional[torch.Tensor] = None,
+        world_points: Optional[torch.Tensor] = None, depths: Optional[torch.Tensor] = None,
+        scale_by_points: bool = True, point_masks: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """data.py:241-335: express the (B, S, 3, 4) w2c extrinsics and the (B, S, H, W, 3)
+    world points in the first camera's frame and, with ``scale_by_points``, divide
+    translations, points and depths by the mean distance of the valid world points.
+    Returns ``(extrinsics (B, S, 3, 4), cam_points, world_points, depths)``.  Host
+    tensors only, as the reference asserts: the datamodule and ``get_sequence_data``
+    call it before the transfer to the device."""
+    from .geometry import closed_form_inverse_se3
+    for t, n in ((extrinsics, "extrinsics"), (cam_points, "cam_points"), (world_points, "world_points"),
+                 (depths, "depths")):
+        check_valid_tensor(t, n)
+    B, S = extrinsics.shape[:2]
+    device = extrinsics.device
+    assert device == torch.device("cpu")
+    homog = torch.cat([extrinsics, torch.zeros((B, S, 1, 4), device=device)], dim=-2)
+    homog[:, :, -1, -1] = 1.0
+    first_inv = closed_form_inverse_se3(homog[:, 0])
+    new_extrinsics = torch.matmul(homog, first_inv.unsqueeze(1))
+    new_world_points = None
+    if world_points is not None:
+        R = extrinsics[:, 0, :3, :3]
+        t = extrinsics[:, 0, :3, 3]
+        new_world_points = world_points @ R.transpose(-1, -2)[:, None, None] + t[:, None, None, None]
+    if not scale_by_points:
+        return new_extrinsics[:, :, :3], cam_points, new_world_points, depths
+    from ..training.loss import check_and_fix_inf_nan
+    # one length unit per batch element: the mean distance of its valid world points from the first camera
+    per_batch = (1, 2, 3)
+    unit = ((new_world_points.norm(dim=-1) * point_masks).sum(dim=per_batch)
+            / (point_masks.sum(dim=per_batch) + 1e-3)).clamp(min=1e-6, max=1e6)
+
+    def in_units(t, name):  # lengths divided by their batch element's unit; non-finite values become 0
+        if t is None:
+            return None
+        return check_and_fix_inf_nan(t / unit.view(-1, *([1] * (t.dim() - 1))), name, hard_max=None)
+    new_extrinsics = new_extrinsics[:, :, :3]
+    new_extrinsics[..., 3] = new_extrinsics[..., 3] / unit.view(-1, 1, 1)
+    return (check_and_fix_inf_nan(new_extrinsics, "new_extrinsics", hard_max=None), in_units(cam_points, "new_cam_points"),
+            in_units(new_world_points, "new_world_points"), in_units(depths, "new_depths"))

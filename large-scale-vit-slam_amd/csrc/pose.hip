@@ -494,7 +494,394 @@ __global__ __launch_bounds__(64) void pose_align_kernel(
   }
 }
 
+// ---- GT alignment of a merged sequence from its poses (alignment.py:131-242, :325-370, :6-59)
+
+// 3x3 symmetric eigen-decomposition (cyclic Jacobi, fp64) and determinant: copies of align.hip's
+// jacobi3 / det3, operation for operation (keep the bodies in step).
+__device__ void jacobi3(double A[3][3], double V[3][3]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
+    const double scale = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
+    if (off <= 1e-300 || off <= 1e-18 * scale) break;
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+        for (int k = 0; k < 3; ++k) {  // A = J^T A J
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 3; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 3; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+__device__ __forceinline__ double det3(const double M[3][3]) {
+  return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+         M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+}
+
+// Umeyama's closed form (alignment.py:6-59) from the centred cross-covariance Sg = E[(y - my)(x - mx)^T]
+// and sigma_x = E|x - mx|^2: R = U diag(1, 1, d) V^T, c = tr(D diag(1, 1, d)) / sigma_x.  The SVD as
+// irls_solve (align.hip) takes it: V from Jacobi on Sg^T Sg, u_k = Sg v_k / |Sg v_k|, u_2 = u_0 x u_1
+// and v_2's sign so that sv_2 >= 0; det(U) is then +1 and d = sign(det(U V^T)) is the reference's
+// det(u) det(v) < 0 test for any valid SVD pair (d v_2 does not depend on v_2's sign).
+__device__ void umeyama3(const double Sg[3][3], double sigma_x, double R[3][3], double* c_out) {
+  double A[3][3], V[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) A[i][j] = Sg[0][i] * Sg[0][j] + Sg[1][i] * Sg[1][j] + Sg[2][i] * Sg[2][j];
+  jacobi3(A, V);
+  int ord[3] = {0, 1, 2};  // eigenvalues descending
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2 - i; ++j)
+      if (A[ord[j]][ord[j]] < A[ord[j + 1]][ord[j + 1]]) {
+        const int tmp = ord[j];
+        ord[j] = ord[j + 1];
+        ord[j + 1] = tmp;
+      }
+  double Vs[3][3], U[3][3], sv[3];
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 3; ++i) Vs[i][k] = V[i][ord[k]];
+  for (int k = 0; k < 2; ++k) {
+    double u[3], nrm = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      u[i] = Sg[i][0] * Vs[0][k] + Sg[i][1] * Vs[1][k] + Sg[i][2] * Vs[2][k];
+      nrm += u[i] * u[i];
+    }
+    nrm = sqrt(nrm);
+    sv[k] = nrm;
+    for (int i = 0; i < 3; ++i) U[i][k] = nrm > 0 ? u[i] / nrm : (i == k ? 1.0 : 0.0);
+  }
+  // rank <= 1 (collinear centres): Sg v_1 is rounding noise, take any unit vector orthogonal to u_0
+  // (irls_solve derives the 2^-40 threshold); the rotation round u_0 is then not determined by the data
+  if (sv[1] <= 0x1p-40 * sv[0]) {
+    int j = 0;
+    for (int i = 1; i < 3; ++i)
+      if (fabs(U[i][0]) < fabs(U[j][0])) j = i;
+    double nrm = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      U[i][1] = (i == j ? 1.0 : 0.0) - U[j][0] * U[i][0];
+      nrm += U[i][1] * U[i][1];
+    }
+    nrm = sqrt(nrm);
+    for (int i = 0; i < 3; ++i) U[i][1] /= nrm;
+  }
+  U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
+  U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
+  U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+  {
+    double u[3];
+    for (int i = 0; i < 3; ++i) u[i] = Sg[i][0] * Vs[0][2] + Sg[i][1] * Vs[1][2] + Sg[i][2] * Vs[2][2];
+    const double proj = u[0] * U[0][2] + u[1] * U[1][2] + u[2] * U[2][2];
+    if (proj < 0)
+      for (int i = 0; i < 3; ++i) Vs[i][2] = -Vs[i][2];
+    sv[2] = fabs(proj);
+  }
+  double UVt[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) UVt[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + U[i][2] * Vs[j][2];
+  const double d = det3(UVt) < 0 ? -1.0 : 1.0;  // the reflection fix (:39-40)
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + d * U[i][2] * Vs[j][2];
+  *c_out = (sv[0] + sv[1] + d * sv[2]) / sigma_x;  // sigma_x == 0: inf or NaN, as the reference's 1 / sigma_x
+}
+
+// One 64-lane workgroup per batch element, lane-stride over frames.  Sums are per-lane fp64
+// partials combined by lane 0 in lane order (no atomics, independent of the grid), every result is
+// rounded to fp32 once.  enc / enc_out are not __restrict__: enc_out may be enc (every read of the
+// first W frames' centres is behind a barrier, and a lane reads frame f's row before it writes it).
+__global__ __launch_bounds__(64) void gt_pose_align_kernel(const float* enc, int ew, const float* __restrict__ gt,
+                                                           int S, int W, int mode, float H, float Wimg,
+                                                           float* __restrict__ scales, float* __restrict__ transform,
+                                                           float* enc_out) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* eb = enc + (int64_t)b * S * ew;
+  const float* gb = gt + (int64_t)b * S * 12;
+  __shared__ double s_part[64][10];
+  __shared__ double s_mean[6];
+  __shared__ Aff s_T;
+  __shared__ float s_c;
+  if (mode == VGGT_GT_POSE_PER_FRAME) {  // alignment.py:131-165
+    for (int f = lane; f < S; f += 64) {
+      const float* e = eb + (int64_t)f * ew;
+      const float* g = gb + (int64_t)f * 12;
+      double sxy = 0.0, sxx = 0.0;
+      for (int i = 0; i < 3; ++i) {
+        sxy += (double)e[i] * (double)g[i * 4 + 3];
+        sxx += (double)e[i] * (double)e[i];
+      }
+      scales[(int64_t)b * S + f] = f == 0 ? 1.0f : fabsf((float)(sxy / sxx));  // 0 / 0: NaN, kept
+    }
+    return;
+  }
+  if (mode == VGGT_GT_POSE_SCALE) {  // alignment.py:206-242 (scale_lse_solver over the first W frames)
+    double sxy = 0.0, sxx = 0.0;
+    for (int f = lane; f < W; f += 64) {
+      const float* e = eb + (int64_t)f * ew;
+      const float* g = gb + (int64_t)f * 12;
+      for (int i = 0; i < 3; ++i) {
+        sxy += (double)e[i] * (double)g[i * 4 + 3];
+        sxx += (double)e[i] * (double)e[i];
+      }
+    }
+    s_part[lane][0] = sxy;
+    s_part[lane][1] = sxx;
+    __syncthreads();
+    if (lane == 0) {
+      double a = 0.0, d = 0.0;
+      for (int k = 0; k < 64; ++k) {
+        a += s_part[k][0];
+        d += s_part[k][1];
+      }
+      scales[b] = fabsf((float)(a / d));  // 0 / 0: NaN, kept
+    }
+    return;
+  }
+  // SIM3 (alignment.py:325-370): Umeyama over the first W camera centres -R^T t, in fp64 from the
+  // fp32 inputs (the prediction's rotation from the raw quaternion, as pose_encoding_to_extri_intri)
+  auto centres = [&](int f, double* x, double* y) {
+    const float* e = eb + (int64_t)f * ew;
+    const float* g = gb + (int64_t)f * 12;
+    const double qi = e[3], qj = e[4], qk = e[5], qr = e[6];
+    const double two_s = 2.0 / (qi * qi + qj * qj + qk * qk + qr * qr);
+    double R[3][3];
+    R[0][0] = 1.0 - two_s * (qj * qj + qk * qk); R[0][1] = two_s * (qi * qj - qk * qr); R[0][2] = two_s * (qi * qk + qj * qr);
+    R[1][0] = two_s * (qi * qj + qk * qr); R[1][1] = 1.0 - two_s * (qi * qi + qk * qk); R[1][2] = two_s * (qj * qk - qi * qr);
+    R[2][0] = two_s * (qi * qk - qj * qr); R[2][1] = two_s * (qj * qk + qi * qr); R[2][2] = 1.0 - two_s * (qi * qi + qj * qj);
+    for (int i = 0; i < 3; ++i) {
+      x[i] = -(R[0][i] * (double)e[0] + R[1][i] * (double)e[1] + R[2][i] * (double)e[2]);
+      y[i] = -((double)g[i] * (double)g[3] + (double)g[4 + i] * (double)g[7] + (double)g[8 + i] * (double)g[11]);
+    }
+  };
+  double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int f = lane; f < W; f += 64) {
+    double x[3], y[3];
+    centres(f, x, y);
+    for (int i = 0; i < 3; ++i) {
+      acc[i] += x[i];
+      acc[3 + i] += y[i];
+    }
+  }
+  for (int j = 0; j < 6; ++j) s_part[lane][j] = acc[j];
+  __syncthreads();
+  if (lane == 0) {
+    for (int j = 0; j < 6; ++j) {
+      double a = 0.0;
+      for (int k = 0; k < 64; ++k) a += s_part[k][j];
+      s_mean[j] = a / (double)W;
+    }
+  }
+  __syncthreads();
+  for (int j = 0; j < 10; ++j) acc[j] = 0.0;
+  for (int f = lane; f < W; f += 64) {
+    double x[3], y[3];
+    centres(f, x, y);
+    for (int i = 0; i < 3; ++i) {
+      x[i] -= s_mean[i];
+      y[i] -= s_mean[3 + i];
+    }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) acc[3 * i + j] += y[i] * x[j];
+    acc[9] += x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+  }
+  for (int j = 0; j < 10; ++j) s_part[lane][j] = acc[j];
+  __syncthreads();
+  if (lane == 0) {
+    double s2[10];
+    for (int j = 0; j < 10; ++j) {
+      double a = 0.0;
+      for (int k = 0; k < 64; ++k) a += s_part[k][j];
+      s2[j] = a / (double)W;
+    }
+    double Sg[3][3], R[3][3], c;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) Sg[i][j] = s2[3 * i + j];
+    umeyama3(Sg, s2[9], R, &c);
+    Aff T;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) T.r[i][j] = (float)R[i][j];
+      T.t[i] = (float)(s_mean[3 + i] - c * (R[i][0] * s_mean[0] + R[i][1] * s_mean[1] + R[i][2] * s_mean[2]));
+    }
+    s_T = T;
+    s_c = (float)c;
+    float* to = transform + (int64_t)b * 16;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) to[i * 4 + j] = T.r[i][j];
+      to[i * 4 + 3] = T.t[i];
+    }
+    to[12] = 0.f; to[13] = 0.f; to[14] = 0.f; to[15] = 1.f;
+    scales[b] = (float)c;
+  }
+  if (enc_out == nullptr) return;
+  __syncthreads();
+  // apply_sim3_alignment (alignment.py:449-489, :528-594) on every frame, fp32 as the reference:
+  // w2c -> c2w, translation x scale, T ., -> w2c, mat_to_quat; the FoV round trip as pose_compose_kernel
+  const Aff T = s_T;
+  const float c = s_c;
+  for (int f = lane; f < S; f += 64) {
+    const float* e = eb + (int64_t)f * ew;
+    float in[9];
+    for (int i = 0; i < 9; ++i) in[i] = e[i];
+    Aff w;
+    quat_to_mat(in + 3, w.r);
+    w.t[0] = in[0]; w.t[1] = in[1]; w.t[2] = in[2];
+    Aff p = inv_se3(w);
+    for (int i = 0; i < 3; ++i) p.t[i] *= c;
+    const Aff a = inv_se3(mul(T, p));
+    float q[4];
+    mat_to_quat(a.r, q);
+    const double fy = ((double)H / 2.0) / tan((double)in[7] / 2.0);
+    const double fx = ((double)Wimg / 2.0) / tan((double)in[8] / 2.0);
+    float* o = enc_out + ((int64_t)b * S + f) * 9;
+    o[0] = a.t[0]; o[1] = a.t[1]; o[2] = a.t[2];
+    o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+    o[7] = (float)(2.0 * atan(((double)H / 2.0) / fy));
+    o[8] = (float)(2.0 * atan(((double)Wimg / 2.0) / fx));
+  }
+}
+
+// ---- ATE / RPE / scale-consistency terms of one update (trajectory_metrics.py:28-48, :154-182, :306-331)
+
+struct M4 {
+  double m[4][4];
+};
+
+__device__ M4 load4(const float* p) {
+  M4 a;
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) a.m[i][j] = (double)p[i * 4 + j];
+  return a;
+}
+
+__device__ M4 mul4(const M4& a, const M4& b) {
+  M4 o;
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j)
+      o.m[i][j] = a.m[i][0] * b.m[0][j] + a.m[i][1] * b.m[1][j] + a.m[i][2] * b.m[2][j] + a.m[i][3] * b.m[3][j];
+  return o;
+}
+
+// General 4x4 inverse by the adjugate over 2x2 sub-determinants (no pivot search, so no
+// run-time indexing); det == 0 gives inf / NaN entries.
+__device__ M4 inv4(const M4& A) {
+  const double(*a)[4] = A.m;
+  const double s0 = a[0][0] * a[1][1] - a[1][0] * a[0][1], s1 = a[0][0] * a[1][2] - a[1][0] * a[0][2];
+  const double s2 = a[0][0] * a[1][3] - a[1][0] * a[0][3], s3 = a[0][1] * a[1][2] - a[1][1] * a[0][2];
+  const double s4 = a[0][1] * a[1][3] - a[1][1] * a[0][3], s5 = a[0][2] * a[1][3] - a[1][2] * a[0][3];
+  const double c5 = a[2][2] * a[3][3] - a[3][2] * a[2][3], c4 = a[2][1] * a[3][3] - a[3][1] * a[2][3];
+  const double c3 = a[2][1] * a[3][2] - a[3][1] * a[2][2], c2 = a[2][0] * a[3][3] - a[3][0] * a[2][3];
+  const double c1 = a[2][0] * a[3][2] - a[3][0] * a[2][2], c0 = a[2][0] * a[3][1] - a[3][0] * a[2][1];
+  const double inv = 1.0 / (s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0);
+  M4 o;
+  o.m[0][0] = (a[1][1] * c5 - a[1][2] * c4 + a[1][3] * c3) * inv;
+  o.m[0][1] = (-a[0][1] * c5 + a[0][2] * c4 - a[0][3] * c3) * inv;
+  o.m[0][2] = (a[3][1] * s5 - a[3][2] * s4 + a[3][3] * s3) * inv;
+  o.m[0][3] = (-a[2][1] * s5 + a[2][2] * s4 - a[2][3] * s3) * inv;
+  o.m[1][0] = (-a[1][0] * c5 + a[1][2] * c2 - a[1][3] * c1) * inv;
+  o.m[1][1] = (a[0][0] * c5 - a[0][2] * c2 + a[0][3] * c1) * inv;
+  o.m[1][2] = (-a[3][0] * s5 + a[3][2] * s2 - a[3][3] * s1) * inv;
+  o.m[1][3] = (a[2][0] * s5 - a[2][2] * s2 + a[2][3] * s1) * inv;
+  o.m[2][0] = (a[1][0] * c4 - a[1][1] * c2 + a[1][3] * c0) * inv;
+  o.m[2][1] = (-a[0][0] * c4 + a[0][1] * c2 - a[0][3] * c0) * inv;
+  o.m[2][2] = (a[3][0] * s4 - a[3][1] * s2 + a[3][3] * s0) * inv;
+  o.m[2][3] = (-a[2][0] * s4 + a[2][1] * s2 - a[2][3] * s0) * inv;
+  o.m[3][0] = (-a[1][0] * c3 + a[1][1] * c1 - a[1][2] * c0) * inv;
+  o.m[3][1] = (a[0][0] * c3 - a[0][1] * c1 + a[0][2] * c0) * inv;
+  o.m[3][2] = (-a[3][0] * s3 + a[3][1] * s1 - a[3][2] * s0) * inv;
+  o.m[3][3] = (a[2][0] * s3 - a[2][1] * s1 + a[2][2] * s0) * inv;
+  return o;
+}
+
+// One 64-lane workgroup per sequence, lane-stride over frames (ATE, scale factor) and over the
+// pairs (i, i + delta) (RPE).  No sums: every output element is an fp64 function of at most four
+// input poses, rounded to fp32 once.
+__global__ __launch_bounds__(64) void trajectory_errors_kernel(
+    const float* __restrict__ pred, const float* __restrict__ gt, int S, int delta, float* __restrict__ ate_vec,
+    float* __restrict__ ate_norm, float* __restrict__ rpe_trans, float* __restrict__ rpe_rot,
+    float* __restrict__ scale_factor) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* pb = pred + (int64_t)b * S * 16;
+  const float* gb = gt + (int64_t)b * S * 16;
+  if (ate_vec != nullptr || ate_norm != nullptr || scale_factor != nullptr) {
+    for (int f = lane; f < S; f += 64) {
+      const float* p = pb + (int64_t)f * 16;
+      const float* g = gb + (int64_t)f * 16;
+      const double px = p[3], py = p[7], pz = p[11], gx = g[3], gy = g[7], gz = g[11];
+      const double dx = px - gx, dy = py - gy, dz = pz - gz;
+      if (ate_vec != nullptr) {
+        float* o = ate_vec + ((int64_t)b * S + f) * 3;
+        o[0] = (float)dx; o[1] = (float)dy; o[2] = (float)dz;
+      }
+      if (ate_norm != nullptr) ate_norm[(int64_t)b * S + f] = (float)sqrt(dx * dx + dy * dy + dz * dz);
+      if (scale_factor != nullptr && f > 0)  // clamp_min(1e-8) on an fp32 tensor: the fp32 value of 1e-8
+        scale_factor[(int64_t)b * (S - 1) + f - 1] =
+            (float)((gx * px + gy * py + gz * pz) / fmax(px * px + py * py + pz * pz, (double)1e-8f));
+    }
+  }
+  if ((rpe_trans == nullptr && rpe_rot == nullptr) || S <= delta) return;
+  const int n = S - delta;
+  for (int i = lane; i < n; i += 64) {
+    const M4 pr = mul4(inv4(load4(pb + (int64_t)i * 16)), load4(pb + (int64_t)(i + delta) * 16));
+    const M4 gr = mul4(inv4(load4(gb + (int64_t)i * 16)), load4(gb + (int64_t)(i + delta) * 16));
+    const M4 err = mul4(inv4(gr), pr);
+    if (rpe_trans != nullptr)
+      rpe_trans[(int64_t)b * n + i] =
+          (float)sqrt(err.m[0][3] * err.m[0][3] + err.m[1][3] * err.m[1][3] + err.m[2][3] * err.m[2][3]);
+    if (rpe_rot != nullptr) {
+      const double c = (err.m[0][0] + err.m[1][1] + err.m[2][2] - 1.0) / 2.0;
+      // torch.clamp keeps a NaN (fmin / fmax would drop it): both comparisons are false for one
+      rpe_rot[(int64_t)b * n + i] = (float)acos(c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c));
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int vggt_gt_pose_align(const float* pose_enc, int enc_width, const float* gt_extr, int B, int S, int W,
+                                  int mode, int img_h, int img_w, float* scales, float* transform,
+                                  float* pose_enc_out, void* stream) {
+  if (B <= 0 || S <= 0 || !pose_enc || !gt_extr || !scales) return VGGT_ERR_SHAPE;
+  if (enc_width != 7 && enc_width != 9) return VGGT_ERR_SHAPE;
+  if (mode != VGGT_GT_POSE_SCALE && mode != VGGT_GT_POSE_PER_FRAME && mode != VGGT_GT_POSE_SIM3)
+    return VGGT_ERR_UNSUPPORTED;
+  if (W == -1) W = S;
+  if (W < 1 || W > S) return VGGT_ERR_SHAPE;
+  if (mode == VGGT_GT_POSE_SIM3) {
+    if (enc_width != 9) return VGGT_ERR_UNSUPPORTED;  // the reference decodes a 9-wide encoding here
+    if (!transform || (pose_enc_out != nullptr && (img_h <= 0 || img_w <= 0))) return VGGT_ERR_SHAPE;
+  }
+  gt_pose_align_kernel<<<B, 64, 0, (hipStream_t)stream>>>(pose_enc, enc_width, gt_extr, S, W, mode, (float)img_h,
+                                                          (float)img_w, scales, transform,
+                                                          mode == VGGT_GT_POSE_SIM3 ? pose_enc_out : nullptr);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+extern "C" int vggt_trajectory_errors(const float* pred_c2w, const float* gt_c2w, int B, int S, int delta,
+                                      float* ate_vec, float* ate_norm, float* rpe_trans, float* rpe_rot,
+                                      float* scale_factor, void* stream) {
+  if (B <= 0 || S <= 0 || delta < 1 || !pred_c2w || !gt_c2w) return VGGT_ERR_SHAPE;
+  trajectory_errors_kernel<<<B, 64, 0, (hipStream_t)stream>>>(pred_c2w, gt_c2w, S, delta, ate_vec, ate_norm,
+                                                              rpe_trans, rpe_rot, scale_factor);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
 
 extern "C" int vggt_pose_align(const float* cam_pose_enc, const float* ctx_pose_enc, int S_prev, const float* gt,
                                int B, int S, int overlap, int H, int W, float* aligned_pose_enc,
