@@ -229,7 +229,8 @@ int vggt_gemm_form(int entry, int epi, int has_out2, int M, int N, int K, int H,
  * (norm1/norm2 of every Block, alignment_head.py:203-206, DPT norm, ...).
  * C must be 256 * {1, 2, 3, 4, 8, 16}; ldx, ldy multiples of 4; x, y 8-byte (bf16) or 16-byte (fp32)
  * aligned, w and b 16-byte aligned.  y == x (same dtype, same ld: in place) is allowed; no other
- * overlap of x and y is.  b is ignored when w is NULL.
+ * overlap of x and y is.  b is ignored when w is NULL.  x or y NULL with M > 0 is VGGT_ERR_SHAPE
+ * (vggt_layernorm_grouped as well).
  */
 int vggt_layernorm(const void* x, int in_dtype, int64_t ldx, const float* w, const float* b, float eps, int M, int C,
                    void* y, int out_dtype, int64_t ldy, void* stream);
@@ -244,6 +245,9 @@ int vggt_layernorm(const void* x, int in_dtype, int64_t ldx, const float* w, con
  * followed by the next block's `norm1(x)` (vggt layers/block.py, ext; the
  * aggregator's frame/global alternation, featureAligned_vggt.py:78-82).
  * C a multiple of 256 in {256, 512, 1024, 2048}.
+ * One check for this form and the two below: x, y or gamma NULL with M > 0 is VGGT_ERR_SHAPE; the
+ * ld of every pointer given a multiple of 4; x, gamma, gamma2, out2, w, b 16-byte and y, y2, xn
+ * 8-byte aligned (VGGT_ERR_ALIGN).
  */
 int vggt_resid_add_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma, float* out2,
                              int64_t ldo2, const float* w, const float* b, float eps, int M, int C, void* xn,
@@ -275,6 +279,11 @@ int vggt_resid_add2_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy,
  * or D (1D), layout cat(angles, angles) as in rope.py:23-44.
  * A position outside [0, tab_len) is clamped to the first / last table row.  b is ignored when w
  * is NULL (no normalisation at all, RoPE only).
+ * One check for this entry point and the three below (vggt_qknorm_rope, the two _out forms): H > 0,
+ * D in {64, 128}, and the data pointers (buf, qkv, src, dst) not NULL when M > 0 (VGGT_ERR_SHAPE);
+ * ld, lds, ldd and col_off multiples of 8, data pointers and tables 16-byte aligned (VGGT_ERR_ALIGN);
+ * qw and kw both given or both NULL; a rope_mode other than VGGT_ROPE_NONE needs pos, cos_tab,
+ * sin_tab, period > 0 and tab_len > 0 (VGGT_ERR_SHAPE); an unknown rope_mode is VGGT_ERR_UNSUPPORTED.
  * Replaces Attention.q_norm/k_norm + rope (vggt attention.py, ext) and
  * CrossAttention q_norm/k_norm + rope1d (cross_attention.py:59-62).
  */

@@ -1,14 +1,19 @@
 // Row LayerNorm and per-head QK-norm + RoPE (include/vggt_mi355x.h:
 // vggt_layernorm, vggt_headnorm_rope).  HBM-bound: one wave per row, 16-B
 // vectorised loads/stores, fp32 two-pass statistics in registers.
-#include "common.h"
+#include "norm_row.h"
 
 namespace {
 
+__device__ __forceinline__ void unpack_bf4(uint2 u, float (&f)[4]) {
+  f[0] = bf2f(u.x & 0xffff);
+  f[1] = bf2f(u.x >> 16);
+  f[2] = bf2f(u.y & 0xffff);
+  f[3] = bf2f(u.y >> 16);
+}
+
 // ---------------------------------------------------------------- LayerNorm
-// NV = C / 256 float4 per lane (C = 256 * NV).
-// Row r of the logical [M, C] input maps to group g = r / G, i = r % G:
-//   x row = g*xgs + xoff + i,  y row = g*ygs + yoff + i   (identity: G = M).
+// NV = C / 256 float4 per lane (C = 256 * NV); rows through a RowMap.
 // x and y carry no __restrict__: the model normalises in place (y == x with equal
 // dtypes and strides; a wave reads its whole row before it stores any of it).
 // fp32 outputs (the fp32 heads: a few hundred rows) take their statistics and the
@@ -16,10 +21,6 @@ namespace {
 // per lane and rsqrtf left a row up to 5 x as far from fp64 as a plain fp32 evaluation
 // (C = 4096, mean 1000: 3.3e-7 against 6.4e-8 of the row norm), which only a bf16
 // rounding hides.  bf16 outputs keep the fp32 statistics (and their bits).
-struct RowMap {
-  int G, xgs, xoff, ygs, yoff;
-};
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -42,18 +43,18 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t l
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;
     if constexpr (IN_BF16) {
-      const uint2 u = *(const uint2*)((const bf16_t*)x + row * ldx + c);
-      v[i][0] = bf2f(u.x & 0xffff);
-      v[i][1] = bf2f(u.x >> 16);
-      v[i][2] = bf2f(u.y & 0xffff);
-      v[i][3] = bf2f(u.y >> 16);
+      unpack_bf4(*(const uint2*)((const bf16_t*)x + row * ldx + c), v[i]);
     } else {
       const f32x4 u = *(const f32x4*)((const float*)x + row * ldx + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[i][j] = u[j];
     }
   }
-  if constexpr (!OUT_BF16) {
+  if constexpr (OUT_BF16) {
+    float mean, rstd;
+    row_stats_f32<NV>(v, eps, mean, rstd);
+    row_affine_store_bf16<NV>(v, mean, rstd, w, b, (bf16_t*)y + orow * ldy, lane);
+  } else {
     double sd = 0.;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -84,44 +85,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t l
       }
       *(f32x4*)((float*)y + orow * ldy + c) = o;
     }
-    return;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += v[i][j];
-  const float mean = wave_sum(s) * (1.f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = v[i][j] - mean;
-      q += d * d;
-    }
-  const float rstd = rsqrtf(wave_sum(q) * (1.f / C) + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = i * 256 + lane * 4;
-    float o[4];
-    if (w) {
-      const f32x4 wv = *(const f32x4*)(w + c);
-      const f32x4 bv = b ? *(const f32x4*)(b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * wv[j] + bv[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd;
-    }
-    if constexpr (OUT_BF16) {
-      uint2 u;
-      u.x = pack_bf2(o[0], o[1]);
-      u.y = pack_bf2(o[2], o[3]);
-      *(uint2*)((bf16_t*)y + orow * ldy + c) = u;
-    } else {
-      *(f32x4*)((float*)y + orow * ldy + c) = f32x4{o[0], o[1], o[2], o[3]};
-    }
   }
 }
 
@@ -147,93 +110,21 @@ int launch_ln(const void* x, int in_bf, int64_t ldx, const float* w, const float
 // deferred two-pass forms give the bits of the two stored passes.
 __device__ __forceinline__ float resid_step(float u, float g, float y) { return u + g * y; }
 
-template <int NV, bool LN>
-__global__ __launch_bounds__(256) void resid_add_ln_kernel(float* __restrict__ x, int64_t ldx,
-                                                           const bf16_t* __restrict__ y, int64_t ldy,
-                                                           const float* __restrict__ gamma, float* __restrict__ out2,
-                                                           int64_t ldo2, const float* __restrict__ w,
-                                                           const float* __restrict__ b, float eps, int M,
-                                                           bf16_t* __restrict__ xn, int64_t ldn) {
-  constexpr int C = NV * 256;
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  float v[NV][4];
-  uint2 yu[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) yu[i] = *(const uint2*)(y + (int64_t)row * ldy + i * 256 + lane * 4);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = i * 256 + lane * 4;
-    const f32x4 u = *(const f32x4*)(x + (int64_t)row * ldx + c);
-    const f32x4 g = *(const f32x4*)(gamma + c);
-    const float yv[4] = {bf2f(yu[i].x & 0xffff), bf2f(yu[i].x >> 16), bf2f(yu[i].y & 0xffff), bf2f(yu[i].y >> 16)};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[i][j] = resid_step(u[j], g[j], yv[j]);
-    *(f32x4*)(x + (int64_t)row * ldx + c) = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
-    if (out2) *(f32x4*)(out2 + (int64_t)row * ldo2 + c) = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
-  }
-  if constexpr (LN) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s += v[i][j];
-    const float mean = wave_sum(s) * (1.f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = v[i][j] - mean;
-        q += d * d;
-      }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / C) + eps);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = i * 256 + lane * 4;
-      float o[4];
-      if (w) {
-        const f32x4 wv = *(const f32x4*)(w + c);
-        const f32x4 bv = b ? *(const f32x4*)(b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * wv[j] + bv[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd;
-      }
-      uint2 u;
-      u.x = pack_bf2(o[0], o[1]);
-      u.y = pack_bf2(o[2], o[3]);
-      *(uint2*)(xn + (int64_t)row * ldn + c) = u;
-    }
-  }
-}
-
-template <int NV>
-void launch_raln(float* x, int64_t ldx, const bf16_t* y, int64_t ldy, const float* gamma, float* out2, int64_t ldo2,
-                 const float* w, const float* b, float eps, int M, bf16_t* xn, int64_t ldn, hipStream_t s) {
-  const int grid = (M + 3) / 4;
-  if (xn)
-    resid_add_ln_kernel<NV, true><<<grid, 256, 0, s>>>(x, ldx, y, ldy, gamma, out2, ldo2, w, b, eps, M, xn, ldn);
-  else
-    resid_add_ln_kernel<NV, false><<<grid, 256, 0, s>>>(x, ldx, y, ldy, gamma, out2, ldo2, w, b, eps, M, xn, ldn);
-}
-
-// The same two row passes of a block with the first one's store of x deferred:
-//  TWO = false (after proj): xn[m] = LayerNorm(x[m] + gamma * y[m]); x is only
+// <TWO, STORE> = <0, 1> is the stored form.  The other two are the same two row
+// passes of a block with the first one's store of x deferred:
+//  <0, 0> (after proj): xn[m] = LayerNorm(x[m] + gamma * y[m]); x is only
 //    read -- x' lives in registers for the statistics.
-//  TWO = true (after fc2): x[m] = (x[m] + gamma * y[m]) + gamma2 * y2[m] with the
+//  <1, 1> (after fc2): x[m] = (x[m] + gamma * y[m]) + gamma2 * y2[m] with the
 //    first pass's y and gamma again (resid_step twice: the bits of the two stored
 //    passes), the kept-layer mirror, and (LN) xn[m] = LayerNorm(x[m]).
 // Per block 180 + 315 MB instead of 270 + 270 MB at 21,984 x 1024.
-template <int NV, bool TWO, bool LN>
-__global__ __launch_bounds__(256) void resid_add_ln_deferred_kernel(
+template <int NV, bool TWO, bool STORE, bool LN>
+__global__ __launch_bounds__(256) void resid_add_ln_kernel(
     float* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ y, int64_t ldy, const float* __restrict__ gamma,
     const bf16_t* __restrict__ y2, int64_t ldy2, const float* __restrict__ gamma2, float* __restrict__ out2,
     int64_t ldo2, const float* __restrict__ w, const float* __restrict__ b, float eps, int M,
     bf16_t* __restrict__ xn, int64_t ldn) {
-  constexpr int C = NV * 256;
+  static_assert(STORE || LN, "a form that stores nothing");
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -249,92 +140,61 @@ __global__ __launch_bounds__(256) void resid_add_ln_deferred_kernel(
     const int c = i * 256 + lane * 4;
     const f32x4 u = *(const f32x4*)(x + (int64_t)row * ldx + c);
     const f32x4 g = *(const f32x4*)(gamma + c);
-    const float yv[4] = {bf2f(yu[i].x & 0xffff), bf2f(yu[i].x >> 16), bf2f(yu[i].y & 0xffff), bf2f(yu[i].y >> 16)};
+    float yv[4];
+    unpack_bf4(yu[i], yv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[i][j] = resid_step(u[j], g[j], yv[j]);
     if constexpr (TWO) {
       const f32x4 g2 = *(const f32x4*)(gamma2 + c);
-      const float yw[4] = {bf2f(yu2[i].x & 0xffff), bf2f(yu2[i].x >> 16), bf2f(yu2[i].y & 0xffff),
-                           bf2f(yu2[i].y >> 16)};
+      unpack_bf4(yu2[i], yv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[i][j] = resid_step(v[i][j], g2[j], yw[j]);
+      for (int j = 0; j < 4; ++j) v[i][j] = resid_step(v[i][j], g2[j], yv[j]);
+    }
+    if constexpr (STORE) {
       *(f32x4*)(x + (int64_t)row * ldx + c) = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
       if (out2) *(f32x4*)(out2 + (int64_t)row * ldo2 + c) = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
     }
   }
   if constexpr (LN) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s += v[i][j];
-    const float mean = wave_sum(s) * (1.f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = v[i][j] - mean;
-        q += d * d;
-      }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / C) + eps);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = i * 256 + lane * 4;
-      float o[4];
-      if (w) {
-        const f32x4 wv = *(const f32x4*)(w + c);
-        const f32x4 bv = b ? *(const f32x4*)(b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * wv[j] + bv[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd;
-      }
-      uint2 u;
-      u.x = pack_bf2(o[0], o[1]);
-      u.y = pack_bf2(o[2], o[3]);
-      *(uint2*)(xn + (int64_t)row * ldn + c) = u;
-    }
+    float mean, rstd;
+    row_stats_f32<NV>(v, eps, mean, rstd);
+    row_affine_store_bf16<NV>(v, mean, rstd, w, b, xn + (int64_t)row * ldn, lane);
   }
 }
 
+using raln_kernel_t = decltype(&resid_add_ln_kernel<1, false, true, true>);
+
 template <int NV>
-void launch_raln_deferred(float* x, int64_t ldx, const bf16_t* y, int64_t ldy, const float* gamma, const bf16_t* y2,
-                          int64_t ldy2, const float* gamma2, float* out2, int64_t ldo2, const float* w,
-                          const float* b, float eps, int M, bf16_t* xn, int64_t ldn, hipStream_t s) {
-  const int grid = (M + 3) / 4;
-  if (!y2)
-    resid_add_ln_deferred_kernel<NV, false, true>
-        <<<grid, 256, 0, s>>>(x, ldx, y, ldy, gamma, y2, ldy2, gamma2, out2, ldo2, w, b, eps, M, xn, ldn);
-  else if (xn)
-    resid_add_ln_deferred_kernel<NV, true, true>
-        <<<grid, 256, 0, s>>>(x, ldx, y, ldy, gamma, y2, ldy2, gamma2, out2, ldo2, w, b, eps, M, xn, ldn);
-  else
-    resid_add_ln_deferred_kernel<NV, true, false>
-        <<<grid, 256, 0, s>>>(x, ldx, y, ldy, gamma, y2, ldy2, gamma2, out2, ldo2, w, b, eps, M, xn, ldn);
+raln_kernel_t raln_kernel(bool two, bool store, bool ln) {
+  if (two) return ln ? resid_add_ln_kernel<NV, true, true, true> : resid_add_ln_kernel<NV, true, true, false>;
+  if (!store) return resid_add_ln_kernel<NV, false, false, true>;
+  return ln ? resid_add_ln_kernel<NV, false, true, true> : resid_add_ln_kernel<NV, false, true, false>;
 }
 
-int raln_deferred(float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma, const void* y2, int64_t ldy2,
-                  const float* gamma2, float* out2, int64_t ldo2, const float* w, const float* b, float eps, int M,
-                  int C, void* xn, int64_t ldn, void* stream) {
+// The three residual entry points: two = vggt_resid_add2_layernorm (y2 and gamma2 required), !store =
+// vggt_resid_add_layernorm_nostore (xn required).
+int raln(bool two, bool store, float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma, const void* y2,
+         int64_t ldy2, const float* gamma2, float* out2, int64_t ldo2, const float* w, const float* b, float eps, int M,
+         int C, void* xn, int64_t ldn, void* stream) {
+  if (two && !y2) return VGGT_ERR_SHAPE;
   if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (C % 256 || C > 4096 || C <= 0 || !x || !y || !gamma || (y2 && !gamma2) || (!y2 && !xn)) return VGGT_ERR_SHAPE;
+  if (C % 256 || C > 4096 || C <= 0 || !x || !y || !gamma || (y2 && !gamma2) || (!store && !xn))
+    return VGGT_ERR_SHAPE;
   if ((ldx % 4) || (ldy % 4) || (y2 && (ldy2 % 4)) || (out2 && (ldo2 % 4)) || (xn && (ldn % 4)))
     return VGGT_ERR_ALIGN;
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)gamma2 | (uintptr_t)out2 | (uintptr_t)w | (uintptr_t)b) % 16 ||
       ((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)xn) % 8)
     return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t *yb = (const bf16_t*)y, *yb2 = (const bf16_t*)y2;
-  bf16_t* nb = (bf16_t*)xn;
+  raln_kernel_t k;
   switch (C / 256) {
-    case 1: launch_raln_deferred<1>(x, ldx, yb, ldy, gamma, yb2, ldy2, gamma2, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 2: launch_raln_deferred<2>(x, ldx, yb, ldy, gamma, yb2, ldy2, gamma2, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 4: launch_raln_deferred<4>(x, ldx, yb, ldy, gamma, yb2, ldy2, gamma2, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 8: launch_raln_deferred<8>(x, ldx, yb, ldy, gamma, yb2, ldy2, gamma2, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
+    case 1: k = raln_kernel<1>(two, store, xn); break;
+    case 2: k = raln_kernel<2>(two, store, xn); break;
+    case 4: k = raln_kernel<4>(two, store, xn); break;
+    case 8: k = raln_kernel<8>(two, store, xn); break;
     default: return VGGT_ERR_SHAPE;
   }
+  k<<<(M + 3) / 4, 256, 0, (hipStream_t)stream>>>(x, ldx, (const bf16_t*)y, ldy, gamma, (const bf16_t*)y2, ldy2, gamma2,
+                                                  out2, ldo2, w, b, eps, M, (bf16_t*)xn, ldn);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -442,26 +302,33 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(const bf16_t* src, i
   }
 }
 
+using hnr_kernel_t = decltype(&headnorm_rope_kernel<64, VGGT_ROPE_NONE>);
+
 template <int D>
-int launch_hnr(const bf16_t* src, int64_t lds, bf16_t* buf, int64_t ld, int col_off, int M, int H, const float* w, const float* b, float eps, int mode,
-               const int32_t* pos, int period, const float* cs, const float* sn, int tab_len, hipStream_t s,
-               int hsplit, const float* w2, const float* b2) {
-  const int grid = (M + 3) / 4;
+hnr_kernel_t hnr_kernel(int mode) {
   switch (mode) {
-    case VGGT_ROPE_NONE:
-      headnorm_rope_kernel<D, VGGT_ROPE_NONE><<<grid, 256, 0, s>>>(src, lds, buf, ld, col_off, M, H, w, b, eps, pos, period, cs,
-                                                                  sn, tab_len, hsplit, w2, b2);
-      break;
-    case VGGT_ROPE_2D:
-      headnorm_rope_kernel<D, VGGT_ROPE_2D><<<grid, 256, 0, s>>>(src, lds, buf, ld, col_off, M, H, w, b, eps, pos, period, cs, sn,
-                                                                tab_len, hsplit, w2, b2);
-      break;
-    case VGGT_ROPE_1D:
-      headnorm_rope_kernel<D, VGGT_ROPE_1D><<<grid, 256, 0, s>>>(src, lds, buf, ld, col_off, M, H, w, b, eps, pos, period, cs, sn,
-                                                                tab_len, hsplit, w2, b2);
-      break;
-    default: return VGGT_ERR_UNSUPPORTED;
+    case VGGT_ROPE_NONE: return headnorm_rope_kernel<D, VGGT_ROPE_NONE>;
+    case VGGT_ROPE_2D: return headnorm_rope_kernel<D, VGGT_ROPE_2D>;
+    case VGGT_ROPE_1D: return headnorm_rope_kernel<D, VGGT_ROPE_1D>;
+    default: return nullptr;
   }
+}
+
+// The four bf16 head-norm entry points: `heads` heads of D columns from column col_off of src into the
+// same columns of dst (dst == src: in place), heads [0, hsplit) with (w, b), the rest with (w2, b2).
+int hnr(const void* src, int64_t lds, void* dst, int64_t ldd, int col_off, int M, int heads, int hsplit, int D,
+        const float* w, const float* b, const float* w2, const float* b2, float eps, int mode, const int32_t* pos,
+        int period, const float* cs, const float* sn, int tab_len, void* stream) {
+  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
+  if (heads <= 0 || (D != 64 && D != 128) || !src || !dst) return VGGT_ERR_SHAPE;
+  if ((lds % 8) || (ldd % 8) || (col_off % 8) || ((uintptr_t)src | (uintptr_t)dst) % 16) return VGGT_ERR_ALIGN;
+  if ((w == nullptr) != (w2 == nullptr)) return VGGT_ERR_SHAPE;
+  if (mode != VGGT_ROPE_NONE && (!pos || !cs || !sn || period <= 0 || tab_len <= 0)) return VGGT_ERR_SHAPE;
+  if (((uintptr_t)cs | (uintptr_t)sn) % 16) return VGGT_ERR_ALIGN;
+  const hnr_kernel_t k = D == 64 ? hnr_kernel<64>(mode) : hnr_kernel<128>(mode);
+  if (!k) return VGGT_ERR_UNSUPPORTED;
+  k<<<(M + 3) / 4, 256, 0, (hipStream_t)stream>>>((const bf16_t*)src, lds, (bf16_t*)dst, ldd, col_off, M, heads, w, b,
+                                                  eps, pos, period, cs, sn, tab_len, hsplit, w2, b2);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -475,7 +342,7 @@ extern "C" int vggt_layernorm_grouped(const void* x, int in_dtype, int64_t ldx, 
   if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
   if (group <= 0) return VGGT_ERR_SHAPE;
   RowMap rm{group, x_group_stride, x_row_offset, y_group_stride, y_row_offset};
-  if (C % 256 || C > 4096 || C <= 0) return VGGT_ERR_SHAPE;
+  if (C % 256 || C > 4096 || C <= 0 || !x || !y) return VGGT_ERR_SHAPE;
   if ((in_dtype != VGGT_DTYPE_F32 && in_dtype != VGGT_DTYPE_BF16) ||
       (out_dtype != VGGT_DTYPE_F32 && out_dtype != VGGT_DTYPE_BF16))
     return VGGT_ERR_UNSUPPORTED;
@@ -505,73 +372,36 @@ extern "C" int vggt_layernorm(const void* x, int in_dtype, int64_t ldx, const fl
 extern "C" int vggt_resid_add_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma,
                                         float* out2, int64_t ldo2, const float* w, const float* b, float eps, int M,
                                         int C, void* xn, int64_t ldn, void* stream) {
-  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (C % 256 || C > 4096 || C <= 0 || !x || !y || !gamma) return VGGT_ERR_SHAPE;
-  if ((ldx % 4) || (ldy % 4) || (out2 && (ldo2 % 4)) || (xn && (ldn % 4))) return VGGT_ERR_ALIGN;
-  if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)out2) % 16 || ((uintptr_t)y | (uintptr_t)xn) % 8)
-    return VGGT_ERR_ALIGN;
-  if ((w && ((uintptr_t)w % 16)) || (b && ((uintptr_t)b % 16))) return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t* yb = (const bf16_t*)y;
-  bf16_t* nb = (bf16_t*)xn;
-  switch (C / 256) {
-    case 1: launch_raln<1>(x, ldx, yb, ldy, gamma, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 2: launch_raln<2>(x, ldx, yb, ldy, gamma, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 4: launch_raln<4>(x, ldx, yb, ldy, gamma, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    case 8: launch_raln<8>(x, ldx, yb, ldy, gamma, out2, ldo2, w, b, eps, M, nb, ldn, s); break;
-    default: return VGGT_ERR_SHAPE;
-  }
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return raln(false, true, x, ldx, y, ldy, gamma, nullptr, 0, nullptr, out2, ldo2, w, b, eps, M, C, xn, ldn, stream);
 }
 
 extern "C" int vggt_resid_add_layernorm_nostore(const float* x, int64_t ldx, const void* y, int64_t ldy,
                                                 const float* gamma, const float* w, const float* b, float eps, int M,
                                                 int C, void* xn, int64_t ldn, void* stream) {
   // the kernel only reads x in this form
-  return raln_deferred(const_cast<float*>(x), ldx, y, ldy, gamma, nullptr, 0, nullptr, nullptr, 0, w, b, eps, M, C, xn,
-                       ldn, stream);
+  return raln(false, false, const_cast<float*>(x), ldx, y, ldy, gamma, nullptr, 0, nullptr, nullptr, 0, w, b, eps, M,
+              C, xn, ldn, stream);
 }
 
 extern "C" int vggt_resid_add2_layernorm(float* x, int64_t ldx, const void* y, int64_t ldy, const float* gamma,
                                          const void* y2, int64_t ldy2, const float* gamma2, float* out2, int64_t ldo2,
                                          const float* w, const float* b, float eps, int M, int C, void* xn,
                                          int64_t ldn, void* stream) {
-  if (!y2) return VGGT_ERR_SHAPE;
-  return raln_deferred(x, ldx, y, ldy, gamma, y2, ldy2, gamma2, out2, ldo2, w, b, eps, M, C, xn, ldn, stream);
+  return raln(true, true, x, ldx, y, ldy, gamma, y2, ldy2, gamma2, out2, ldo2, w, b, eps, M, C, xn, ldn, stream);
 }
 
 extern "C" int vggt_headnorm_rope(void* buf, int64_t ld, int col_off, int M, int H, int D, const float* w,
                                   const float* b, float eps, int rope_mode, const int32_t* pos, int period,
                                   const float* cos_tab, const float* sin_tab, int tab_len, void* stream) {
-  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (H <= 0 || (D != 64 && D != 128)) return VGGT_ERR_SHAPE;
-  if ((ld % 8) || (col_off % 8) || ((uintptr_t)buf % 16)) return VGGT_ERR_ALIGN;
-  if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16) return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return launch_hnr<64>((const bf16_t*)buf, ld, (bf16_t*)buf, ld, col_off, M, H, w, b, eps, rope_mode, pos, period, cos_tab, sin_tab,
-                                     tab_len, s, H, w, b);
-  return launch_hnr<128>((const bf16_t*)buf, ld, (bf16_t*)buf, ld, col_off, M, H, w, b, eps, rope_mode, pos, period, cos_tab, sin_tab, tab_len, s,
-                         H, w, b);
+  return hnr(buf, ld, buf, ld, col_off, M, H, H, D, w, b, w, b, eps, rope_mode, pos, period, cos_tab, sin_tab, tab_len,
+             stream);
 }
 
 extern "C" int vggt_qknorm_rope(void* qkv, int64_t ld, int M, int H, int D, const float* qw, const float* qb,
                                 const float* kw, const float* kb, float eps, int rope_mode, const int32_t* pos,
                                 int period, const float* cos_tab, const float* sin_tab, int tab_len, void* stream) {
-  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (H <= 0 || (D != 64 && D != 128)) return VGGT_ERR_SHAPE;
-  if ((ld % 8) || ((uintptr_t)qkv % 16)) return VGGT_ERR_ALIGN;
-  if ((qw == nullptr) != (kw == nullptr)) return VGGT_ERR_SHAPE;
-  if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16) return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return launch_hnr<64>((const bf16_t*)qkv, ld, (bf16_t*)qkv, ld, 0, M, 2 * H, qw, qb, eps, rope_mode, pos, period, cos_tab,
-                                     sin_tab, tab_len, s, H, kw, kb);
-  return launch_hnr<128>((const bf16_t*)qkv, ld, (bf16_t*)qkv, ld, 0, M, 2 * H, qw, qb, eps, rope_mode, pos, period, cos_tab, sin_tab, tab_len,
-                         s, H, kw, kb);
+  return hnr(qkv, ld, qkv, ld, 0, M, 2 * H, H, D, qw, qb, kw, kb, eps, rope_mode, pos, period, cos_tab, sin_tab,
+             tab_len, stream);
 }
 
 // Out-of-place form of vggt_qknorm_rope: the q|k columns [0, 2*H*D) of src
@@ -582,18 +412,8 @@ extern "C" int vggt_qknorm_rope_out(const void* src, int64_t lds, void* dst, int
                                     const float* qw, const float* qb, const float* kw, const float* kb, float eps,
                                     int rope_mode, const int32_t* pos, int period, const float* cos_tab,
                                     const float* sin_tab, int tab_len, void* stream) {
-  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (H <= 0 || (D != 64 && D != 128)) return VGGT_ERR_SHAPE;
-  if ((lds % 8) || (ldd % 8) || ((uintptr_t)src % 16) || ((uintptr_t)dst % 16)) return VGGT_ERR_ALIGN;
-  if ((qw == nullptr) != (kw == nullptr)) return VGGT_ERR_SHAPE;
-  if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16) return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return launch_hnr<64>((const bf16_t*)src, lds, (bf16_t*)dst, ldd, 0, M, 2 * H, qw, qb, eps, rope_mode,
-                                     pos, period, cos_tab, sin_tab, tab_len, s, H, kw, kb);
-  return launch_hnr<128>((const bf16_t*)src, lds, (bf16_t*)dst, ldd, 0, M, 2 * H, qw, qb, eps, rope_mode, pos, period,
-                         cos_tab, sin_tab, tab_len, s, H, kw, kb);
+  return hnr(src, lds, dst, ldd, 0, M, 2 * H, H, D, qw, qb, kw, kb, eps, rope_mode, pos, period, cos_tab, sin_tab,
+             tab_len, stream);
 }
 
 // Out-of-place form of vggt_headnorm_rope: H heads of D columns starting at
@@ -602,15 +422,6 @@ extern "C" int vggt_headnorm_rope_out(const void* src, int64_t lds, void* dst, i
                                       const float* w, const float* b, float eps, int rope_mode, const int32_t* pos,
                                       int period, const float* cos_tab, const float* sin_tab, int tab_len,
                                       void* stream) {
-  if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (H <= 0 || (D != 64 && D != 128)) return VGGT_ERR_SHAPE;
-  if ((lds % 8) || (ldd % 8) || ((uintptr_t)src % 16) || ((uintptr_t)dst % 16)) return VGGT_ERR_ALIGN;
-  if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
-    return VGGT_ERR_SHAPE;
-  if (((uintptr_t)cos_tab | (uintptr_t)sin_tab) % 16) return VGGT_ERR_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return launch_hnr<64>((const bf16_t*)src, lds, (bf16_t*)dst, ldd, 0, M, H, w, b, eps, rope_mode, pos,
-                                     period, cos_tab, sin_tab, tab_len, s, H, w, b);
-  return launch_hnr<128>((const bf16_t*)src, lds, (bf16_t*)dst, ldd, 0, M, H, w, b, eps, rope_mode, pos, period,
-                         cos_tab, sin_tab, tab_len, s, H, w, b);
+  return hnr(src, lds, dst, ldd, 0, M, H, H, D, w, b, w, b, eps, rope_mode, pos, period, cos_tab, sin_tab, tab_len,
+             stream);
 }

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "mfma_frag.h"
+#include "norm_row.h"
 
 namespace {
 
@@ -247,22 +248,17 @@ __global__ __launch_bounds__(256) void transpose_b16_kernel(const uint16_t* __re
 
 // ------------------------------------------------------------ LayerNorm backward
 // One wave per row (C = 256*NV), 4 waves per block; block y covers rows
-// [blk*rpb, blk*rpb + rpb).  Row mapping as the forward's RowMap: logical
-// row r -> group g = r / G, i = r % G;  x / dx row = g*xgs + xoff + i,
-// dy row = g*ygs + yoff + i.
+// [blk*rpb, blk*rpb + rpb).  Row mapping as the forward's (RowMap): x / dx
+// rows by (xgs, xoff), dy rows by (ygs, yoff).
 //   xhat = (x - mean) * rstd;  gdy = dy * w
 //   dx  (+)= rstd * (gdy - mean(gdy) - xhat * mean(gdy * xhat))
 //   dw  += dy * xhat;   db += dy      (partials per block, finalize later)
-struct RowMap2 {
-  int G, xgs, xoff, ygs, yoff;
-};
-
 template <int NV>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ x, int xdt, int64_t ldx,
                                                      const float* __restrict__ w, float eps,
                                                      const void* __restrict__ dy, int ydt, int64_t ldy,
                                                      void* __restrict__ dx, int dxdt, int64_t lddx, int accumulate,
-                                                     int M, RowMap2 rm, int rpb, float* __restrict__ part) {
+                                                     int M, RowMap rm, int rpb, float* __restrict__ part) {
   constexpr int C = NV * 256;
   __shared__ float red[2][4][C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -291,21 +287,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ x,
       load4(dy, ydt, yr * ldy + c, g[i]);
       if (accumulate) load4(dx, dxdt, xr * lddx + c, prev[i]);  // issued with the operands, used at the end
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s += v[i][j];
-    const float mean = wave_sum(s) * (1.f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = v[i][j] - mean;
-        q += d * d;
-      }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / C) + eps);
+    float mean, rstd;
+    row_stats_f32<NV>(v, eps, mean, rstd);  // the forward's statistics, recomputed
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ x,
 
 template <int NV>
 void launch_ln_bwd(const void* x, int xdt, int64_t ldx, const float* w, float eps, const void* dy, int ydt,
-                   int64_t ldy, void* dx, int dxdt, int64_t lddx, int acc, int M, RowMap2 rm, int nblk, int rpb,
+                   int64_t ldy, void* dx, int dxdt, int64_t lddx, int acc, int M, RowMap rm, int nblk, int rpb,
                    float* part, hipStream_t s) {
   ln_bwd_kernel<NV><<<nblk, 256, 0, s>>>(x, xdt, ldx, w, eps, dy, ydt, ldy, dx, dxdt, lddx, acc, M, rm, rpb, part);
 }
@@ -1057,7 +1040,7 @@ extern "C" int vggt_layernorm_bwd(const void* x, int xdtype, int64_t ldx, const 
   const bool want = dw || db;
   if (want && (!ws || ws_bytes < (size_t)2 * nblk * C * sizeof(float))) return VGGT_ERR_SHAPE;
   const int rpb = (M + nblk - 1) / nblk;
-  RowMap2 rm{group, x_group_stride, x_row_offset, y_group_stride, y_row_offset};
+  RowMap rm{group, x_group_stride, x_row_offset, y_group_stride, y_row_offset};
   hipStream_t s = (hipStream_t)stream;
   float* part = want ? (float*)ws : nullptr;
   switch (C / 256) {

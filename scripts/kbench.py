@@ -101,6 +101,20 @@ def main():
         us = timeit(lambda: N.qknorm_rope(qkv, H, D, qw, qb, kw, kb, 1e-5, rp.mode, rp.pos, rp.period, rp.cos, rp.sin),
                     args.reps)
         res["qknorm_rope"] = {"us": round(us, 1), "gbs": round(M * 2 * C * 4 / us / 1e3, 1)}
+        # the residual forms; gbs from the bytes each moves per element (x f32, y / xn bf16)
+        yb, yb2 = torch.randn(M, C, device=dev).bfloat16(), torch.randn(M, C, device=dev).bfloat16()
+        gam, gam2 = torch.rand(C, device=dev) * 1e-3, torch.rand(C, device=dev) * 1e-3
+        for name, nbytes, fn in (
+                ("resid_add_layernorm", 12, lambda: N.resid_add_layernorm(xf, yb, gam, None, w, b, 1e-5, y)),
+                ("resid_add_layernorm_nostore", 8, lambda: N.resid_add_layernorm_nostore(xf, yb, gam, w, b, 1e-5, y)),
+                ("resid_add2_layernorm", 14,
+                 lambda: N.resid_add2_layernorm(xf, yb, gam, yb2, gam2, None, w, b, 1e-5, y))):
+            us = timeit(fn, args.reps)
+            res[name] = {"us": round(us, 1), "gbs": round(M * C * nbytes / us / 1e3, 1)}
+        dy, dx = torch.randn(M, C, device=dev).bfloat16(), torch.empty(M, C, device=dev)
+        dw, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        us = timeit(lambda: N.layernorm_bwd(xf, w, 1e-5, dy, dx, False, dw, db), args.reps)
+        res["layernorm_bwd"] = {"us": round(us, 1), "gbs": round(M * C * 10 / us / 1e3, 1)}
     if "attn" in only:
         qkv = (torch.randn(M, 3 * C, device=dev)).bfloat16()
         o = torch.empty(M, C, device=dev, dtype=torch.bfloat16)

@@ -27,7 +27,11 @@ Entry point, paths reached, rule:
   vggt_resid_add_layernorm, _nostore, add2   NV in {1, 2, 4, 8}; x' = x + gamma y by the one-op
         rule, out2 bitwise x', xn by the model rule against the fp64 LayerNorm of the stored x';
         b without w must change nothing (b is ignored when w is NULL); the deferred forms bitwise
-        the stored forms, x untouched by _nostore; all five matrices strided.
+        the stored forms, x untouched by _nostore; all five matrices strided.  With gamma = 0 the
+        xn is bitwise vggt_layernorm of x (one statistics routine, csrc/norm_row.h).
+  error returns   every rule of the residual check and of the head-norm check
+        broken once per entry point that has the argument, NULL data pointers included; nothing
+        may be written.
   vggt_qknorm_rope(_out), vggt_headnorm_rope(_out)   64 / (D / 8) heads per wave pass: D = 64
         with 10 heads (8 + 2, hsplit 5 inside pass 0) and 18 heads (8 + 8 + 2, hsplit 9 inside
         pass 1), D = 128 with 6 (4 + 2, hsplit 3) and 10 heads (4 + 4 + 2, hsplit 5 inside pass
@@ -47,9 +51,9 @@ import math
 import pytest
 import torch
 
-from edge_rules import (BF, EPS, ERR_ALIGN, ERR_SHAPE, ERR_UNSUPPORTED, F32, F64, FIG, HN_CFG, NAN, SENT, Box, _bits,
-                        _done, _dtn, _eq_bits, _fig, _figures, _gam, _gen, _guarded, _guards_ok, _hn_args, _hn_host,
-                        _interval, _model_rule, _raises, _within)
+from edge_rules import (BF, EPS, ERR_ALIGN, ERR_SHAPE, ERR_UNSUPPORTED, F32, F64, FIG, HN_CFG, NAN, OK, POS, SENT, TAB,
+                        Box, _bits, _done, _dtn, _eq_bits, _fig, _figures, _gam, _gen, _guarded, _guards_ok, _hn_args,
+                        _hn_host, _interval, _model_rule, _raises, _within)
 
 pytestmark = pytest.mark.gpu
 
@@ -221,7 +225,152 @@ def test_layernorm_error_returns(N):
     assert rc(ldx=4401) == ERR_ALIGN and rc(ldy=4402) == ERR_ALIGN
     assert rc(xo=1) == ERR_ALIGN  # x 4 bytes off
     assert rc(wo=1) == ERR_ALIGN and rc(bo=2) == ERR_ALIGN  # w / b feed 16-B loads
+    assert L.vggt_layernorm(None, 0, 4400, None, None, EPS, 4, 256, N._p(buf), 0, 4400, st) == ERR_SHAPE
+    assert L.vggt_layernorm(N._p(buf), 0, 4400, None, None, EPS, 4, 256, None, 0, 4400, st) == ERR_SHAPE
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------ error returns of the residual and head-norm forms
+# The case tables work on addresses, so that they can be walked without a device as well (every
+# rejected call returns before anything is launched).  Each case breaks exactly one rule.  The
+# buffers behind the addresses are 16 x 4400 elements (vectors 4404 floats, the tables in their
+# middle) and the calls use 4 rows, so that a call whose check was lost stays inside them.
+ERR_LD = 4400
+RESID_ARGS = {
+    "vggt_resid_add_layernorm": "x ldx y ldy gamma out2 ldo2 w b eps M C xn ldn",
+    "vggt_resid_add_layernorm_nostore": "x ldx y ldy gamma w b eps M C xn ldn",
+    "vggt_resid_add2_layernorm": "x ldx y ldy gamma y2 ldy2 gamma2 out2 ldo2 w b eps M C xn ldn",
+}
+HN_ARGS = {
+    "vggt_headnorm_rope": "buf ld col_off M H D w b eps mode pos period cos sin tab",
+    "vggt_qknorm_rope": "buf ld M H D w b kw kb eps mode pos period cos sin tab",
+    "vggt_qknorm_rope_out": "src lds dst ldd M H D w b kw kb eps mode pos period cos sin tab",
+    "vggt_headnorm_rope_out": "src lds dst ldd M H D w b eps mode pos period cos sin tab",
+}
+
+
+def _off(addr, nbytes):
+    return addr + nbytes
+
+
+def _resid_error_cases(a):
+    """(entry point, what is wrong, arguments by name, expected return); `a` maps names to addresses."""
+    base = dict(x=a["x"], y=a["y"], gamma=a["gamma"], y2=a["y2"], gamma2=a["gamma2"], out2=a["out2"], w=a["w"],
+                b=a["b"], xn=a["xn"], ldx=ERR_LD, ldy=ERR_LD, ldy2=ERR_LD, ldo2=ERR_LD, ldn=ERR_LD, eps=EPS, M=4, C=256)
+    changes = [({"C": c}, ERR_SHAPE) for c in (128, 320, 4352)]
+    changes += [({"M": -1}, ERR_SHAPE), ({"M": 0}, OK)]
+    changes += [({k: None}, ERR_SHAPE) for k in ("x", "y", "gamma")]
+    changes += [({k: ERR_LD + 1}, ERR_ALIGN) for k in ("ldx", "ldy", "ldy2", "ldo2", "ldn")]
+    changes += [({k: _off(base[k], 4)}, ERR_ALIGN) for k in ("x", "gamma", "gamma2", "out2", "w", "b")]
+    changes += [({k: _off(base[k], 2)}, ERR_ALIGN) for k in ("y", "y2", "xn")]
+    cases = []
+    for entry, names in RESID_ARGS.items():
+        names = names.split()
+        for ch, want in changes:
+            if all(k in names for k in ch):
+                cases.append((entry, ch, {**base, **ch}, want))
+    two, nostore = "vggt_resid_add2_layernorm", "vggt_resid_add_layernorm_nostore"
+    cases.append((two, "add2 without y2", {**base, "y2": None}, ERR_SHAPE))
+    cases.append((two, "y2 without gamma2", {**base, "gamma2": None}, ERR_SHAPE))
+    cases.append((nostore, "_nostore without xn", {**base, "xn": None}, ERR_SHAPE))
+    return cases
+
+
+def _hn_error_cases(a):
+    base = dict(buf=a["y"], src=a["y"], dst=a["xn"], ld=ERR_LD, lds=ERR_LD, ldd=ERR_LD, col_off=8, M=4, H=2, D=64,
+                w=a["w"], b=a["b"], kw=a["gamma"], kb=a["gamma2"], eps=EPS, mode=1, pos=a["pos"], period=3,
+                cos=a["cos"], sin=a["sin"], tab=TAB)
+    changes = [({"D": d}, ERR_SHAPE) for d in (32, 96)]
+    changes += [({"H": 0}, ERR_SHAPE), ({"M": -1}, ERR_SHAPE)]
+    changes += [({k: ERR_LD - 4}, ERR_ALIGN) for k in ("ld", "lds", "ldd")]  # 4396 = 8 k + 4
+    changes += [({"col_off": 4}, ERR_ALIGN)]
+    changes += [({k: _off(base[k], 2)}, ERR_ALIGN) for k in ("buf", "src", "dst")]
+    changes += [({"w": None}, ERR_SHAPE), ({"kw": None}, ERR_SHAPE)]  # kw without qw, qw without kw
+    changes += [({k: None}, ERR_SHAPE) for k in ("pos", "cos", "sin")]
+    changes += [({"period": 0}, ERR_SHAPE), ({"tab": 0}, ERR_SHAPE)]
+    changes += [({k: _off(base[k], 4)}, ERR_ALIGN) for k in ("cos", "sin")]
+    changes += [({"mode": 3}, ERR_UNSUPPORTED)]
+    changes += [({k: None}, ERR_SHAPE) for k in ("buf", "src", "dst")]
+    cases = []
+    for entry, names in HN_ARGS.items():
+        names = names.split()
+        for ch, want in changes:
+            if ("w" in ch or "kw" in ch) and "kw" not in names:
+                continue  # one weight set: w NULL only switches the norm off
+            if all(k in names for k in ch):
+                cases.append((entry, ch, {**base, **ch}, want))
+    return cases
+
+
+def _call(L, names, entry, args, stream):
+    return getattr(L, entry)(*[args[k] for k in names[entry].split()], stream)
+
+
+def _error_buffers():
+    g = _gen(13)
+    f32 = {k: torch.randn(16, ERR_LD, generator=g).cuda() for k in ("x", "out2")}
+    bf = {k: torch.randn(16, ERR_LD, generator=g).to(BF).cuda() for k in ("y", "y2", "xn")}
+    vec = {k: torch.randn(ERR_LD + 4, generator=g).cuda() for k in ("gamma", "gamma2", "w", "b", "cos", "sin")}
+    bufs = {**f32, **bf, **vec, "pos": torch.tensor(POS[2], dtype=torch.int32).cuda()}
+    addr = {k: t.data_ptr() for k, t in bufs.items()}
+    addr["cos"] += 4 * 2048  # room on both sides of the tables
+    addr["sin"] += 4 * 2048
+    return bufs, addr
+
+
+def _run_error_cases(N, cases, names):
+    L, st = N.lib(), N._stream()
+    bufs, addr = _error_buffers()
+    before = {k: _bits(t.cpu()) for k, t in bufs.items()}
+    bad = []
+    for entry, what, args, want in cases(addr):
+        rc = _call(L, names, entry, args, st)
+        if rc != want:
+            bad.append(f"{entry} {what}: returned {rc}, want {want}")
+    torch.cuda.synchronize()
+    for k, t in bufs.items():
+        if not torch.equal(_bits(t.cpu()), before[k]):
+            bad.append(f"buffer {k} was written by a rejected call")
+    assert not bad, "\n".join(bad)
+    return L, st, bufs, addr
+
+
+def test_resid_error_returns(N):
+    L, st, bufs, addr = _run_error_cases(N, _resid_error_cases, RESID_ARGS)
+    # ldo2 is looked at only with out2: these two calls run (x' = x + gamma y, xn written)
+    ok = next(c for c in _resid_error_cases(addr) if c[1] == {"ldo2": ERR_LD + 1})[2]
+    for entry in ("vggt_resid_add_layernorm", "vggt_resid_add2_layernorm"):
+        assert _call(L, RESID_ARGS, entry, {**ok, "out2": None}, st) == OK
+    torch.cuda.synchronize()
+
+
+def test_headnorm_error_returns(N):
+    _run_error_cases(N, _hn_error_cases, HN_ARGS)
+
+
+@pytest.mark.parametrize("C", [256, 1024, 2048])
+def test_resid_xn_is_layernorm_of_x(N, C):
+    """One statistics routine, seen from outside: with gamma = 0 (x' = x + 0 y = x bit for bit, y
+    finite) the xn of vggt_resid_add_layernorm is bit for bit vggt_layernorm (fp32 -> bf16) of x."""
+    errs = []
+    g = _gen(14, C)
+    wd, bd = (1 + 0.2 * torch.randn(C, generator=g)).cuda(), (0.3 * torch.randn(C, generator=g)).cuda()
+    zero = torch.zeros(C, device="cuda")
+    for M in (1, 5):
+        x, y, _ = _raln_inputs(M, C, g)
+        x[0, :2] = 1.0  # the 0.0 / -0.0 of _raln_inputs: -0 + 0 y would become +0
+        for w, b in ((wd, bd), (None, None)):
+            tag = f"C={C} M={M} {'wb' if w is not None else 'none'}"
+            xb, yb = Box(x, NAN), Box(y, NAN, cols=(16, 8))
+            n0 = Box(torch.zeros(M, C, dtype=BF), SENT, cols=(24, 8))
+            n1 = Box(torch.zeros(M, C, dtype=BF), SENT, cols=(8, 32))
+            N.layernorm(xb.v, w, b, EPS, n0.v)
+            N.resid_add_layernorm(xb.v, yb.v, zero, None, w, b, EPS, n1.v)
+            _eq_bits(errs, tag + " x after gamma = 0", xb.got(), x)
+            _eq_bits(errs, tag + " xn vs layernorm", n1.got(), n0.got())
+            if not (n0.intact() and n1.intact() and xb.intact()):
+                errs.append(tag + ": padding overwritten")
+    _done(errs)
 
 
 # ================================================================== 2. residual add + layernorm
