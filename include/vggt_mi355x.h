@@ -917,6 +917,15 @@ int vggt_trajectory_errors(const float* pred_c2w, const float* gt_c2w, int B, in
  * into parameter gradients are deterministic: fixed row chunks write partial
  * sums to `ws` (>= the size the matching *_workspace_bytes returns) and a
  * second pass ADDS them, in chunk order, to the fp32 gradient buffer.
+ *
+ * Error returns of the entries below from vggt_attention_small_bwd on (one
+ * check per entry, before anything is launched or written): a dimension or
+ * workspace rule broken, or a required pointer NULL with M > 0:
+ * VGGT_ERR_SHAPE; a dtype argument that is neither VGGT_DTYPE_F32 nor
+ * VGGT_DTYPE_BF16: VGGT_ERR_UNSUPPORTED; a leading dimension or a base pointer
+ * off the stated alignment: VGGT_ERR_ALIGN.  Pointers called "may be NULL" are
+ * the optional ones; every other pointer is required.  Each comment states its
+ * entry's rules and its answer for M == 0.
  * ====================================================================== */
 
 /* Forward attention as vggt_attention_fwd (exact scores, no Q prescale) that
@@ -954,6 +963,9 @@ int vggt_attention_bwd(const void* q, int64_t ldq, int64_t q_bstride, const void
  * nothing written (D = 128: nq = 29, nk = 28 fits, 29 x 29 does not; D = 64:
  * nq = 1, nk = 125 does not).  D even; operand rows that are all 16-B aligned
  * with D % 8 == 0 are read 16 B per lane, any other layout element by element.
+ * VGGT_ERR_SHAPE: batch, heads, nq, nk or D < 1 (no empty call), D odd, the LDS
+ * limit, any of the seven pointers NULL; VGGT_ERR_UNSUPPORTED: dtype;
+ * VGGT_ERR_ALIGN: lddq or lddkv odd, dq, dk or dv off 4 bytes.
  */
 int vggt_attention_small_bwd(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                              int64_t k_bstride, const void* v, int64_t ldv, const void* dout, int64_t ldo,
@@ -969,6 +981,11 @@ int vggt_attention_small_bwd(const void* q, int64_t ldq, int64_t q_bstride, cons
  * y_row_offset + i).  accumulate: bit VGGT_LN_BWD_DX_ACCUMULATE (1) dx += (f32
  * only, else dx =); dw/db (may be NULL) get the parameter gradients added, or
  * written with bit VGGT_LN_BWD_PARAMS_WRITE (2).  C % 256 == 0, C <= 1024.
+ * M == 0: VGGT_OK, nothing launched.  VGGT_ERR_SHAPE: M < 0, C not 256, 512 or
+ * 1024, group < 1, x, dy or dx NULL, ws NULL or below
+ * vggt_layernorm_bwd_workspace_bytes when dw or db is given;
+ * VGGT_ERR_UNSUPPORTED: a dtype, an unknown accumulate bit, dx += into bf16;
+ * VGGT_ERR_ALIGN: ldx, ldy or lddx % 4, x, dy or dx off 8 bytes.
  */
 #define VGGT_LN_BWD_DX_ACCUMULATE 1
 #define VGGT_LN_BWD_PARAMS_WRITE 2
@@ -985,6 +1002,12 @@ int vggt_layernorm_bwd(const void* x, int xdtype, int64_t ldx, const float* w, f
  * out, in place.  Heads [0, hsplit) use w0 (gradients into dw0/db0), heads
  * [hsplit, H) use w1 (dw1/db1); NULL w = no norm.  RoPE conventions as
  * vggt_headnorm_rope.
+ * M == 0: VGGT_OK, nothing launched.  VGGT_ERR_SHAPE: M < 0, H < 1, D not 64 or
+ * 128, hsplit outside [0, H], pre or grad NULL, with a RoPE mode pos, cos_tab or
+ * sin_tab NULL or period or tab_len < 1, ws NULL or below
+ * vggt_headnorm_rope_bwd_workspace_bytes when a norm and a gradient pointer are
+ * given; VGGT_ERR_UNSUPPORTED: dtype, an unknown rope_mode; VGGT_ERR_ALIGN: ldp
+ * or ldg % 8, pre or grad off 16 bytes.
  */
 size_t vggt_headnorm_rope_bwd_workspace_bytes(int M, int D);
 int vggt_headnorm_rope_bwd(const void* pre, int64_t ldp, void* grad, int64_t ldg, int dtype, int M, int H, int hsplit,
@@ -992,10 +1015,13 @@ int vggt_headnorm_rope_bwd(const void* pre, int64_t ldp, void* grad, int64_t ldg
                            int period, const float* cos_tab, const float* sin_tab, int tab_len, float* dw0,
                            float* db0, float* dw1, float* db1, void* ws, size_t ws_bytes, void* stream);
 
-/* Column-reduction workspace for vggt_colsum / vggt_layerscale_bwd / vggt_gelu_bwd. */
+/* Column-reduction workspace for vggt_colsum / vggt_layerscale_bwd / vggt_gelu_bwd.  The three share
+ * their rules: M < 1 (M == 0 included), N < 1 or N % 4, a required pointer NULL, ws NULL or too small:
+ * VGGT_ERR_SHAPE; a dtype: VGGT_ERR_UNSUPPORTED; a leading dimension % 4, a bf16 / f32 matrix off 8 bytes
+ * (dout and gamma of vggt_layerscale_bwd: 16): VGGT_ERR_ALIGN. */
 size_t vggt_colred_workspace_bytes(int M, int N);
 
-/* out[n] (+)= sum_m x[m, n]  (Linear bias gradients).  N % 4 == 0. */
+/* out[n] (+)= sum_m x[m, n]  (Linear bias gradients).  N % 4 == 0.  x and out are required. */
 int vggt_colsum(const void* x, int dtype, int64_t ldx, int M, int N, float* out, int accumulate, void* ws,
                 size_t ws_bytes, void* stream);
 
@@ -1003,45 +1029,57 @@ int vggt_colsum(const void* x, int dtype, int64_t ldx, int M, int N, float* out,
  * LayerScale + residual backward (x + gamma * branch, vggt layers/block.py /
  * cross_attention.py:130-131): dbranch = gamma * dout (rounded to odtype),
  * dgamma += sum_m dout * branch, dbias += sum_m dbranch (the bias gradient of
- * the Linear that produced the branch).  dgamma / dbias may be NULL.
+ * the Linear that produced the branch).  dgamma / dbias may be NULL; dout, branch, gamma and dbranch
+ * are required.
  */
 int vggt_layerscale_bwd(const float* dout, int64_t ldd, const void* branch, int bdtype, int64_t ldb,
                         const float* gamma, void* dbranch, int odtype, int64_t ldo, int M, int N, float* dgamma,
                         float* dbias, void* ws, size_t ws_bytes, void* stream);
 
-/* y = GELU(x) (exact erf), any f32/bf16 combination (Mlp.act, unfused training form). */
+/* y = GELU(x) (exact erf), any f32/bf16 combination (Mlp.act, unfused training form).
+ * M == 0: VGGT_OK, nothing launched.  VGGT_ERR_SHAPE: M < 0, N < 1 or N % 4, x or y NULL;
+ * VGGT_ERR_UNSUPPORTED: a dtype; VGGT_ERR_ALIGN: ldx or ldy % 4, x or y off 8 bytes. */
 int vggt_gelu_fwd(const void* x, int xdtype, int64_t ldx, void* y, int ydtype, int64_t ldy, int M, int N,
                   void* stream);
 
 /* dpre = dh * GELU'(pre) (rounded to odtype); dbias += sum_m dpre (fc1 bias gradient; may be NULL).
  * dpre may be dh itself (same pointer, leading dimension and dtype: in place, as the MLP backward
  * calls it) and then holds the same bits as the out-of-place call; it must not overlap pre, nor dh
- * in any other way. */
+ * in any other way.  dh, pre and dpre are required. */
 int vggt_gelu_bwd(const void* dh, int dhdtype, int64_t lddh, const void* pre, int predtype, int64_t ldp, void* dpre,
                   int odtype, int64_t ldo, int M, int N, float* dbias, void* ws, size_t ws_bytes, void* stream);
 
-/* x_f32[m, n] += gamma[n] * branch[m, n]  (LayerScale residual add with a saved branch). */
+/* x_f32[m, n] += gamma[n] * branch[m, n]  (LayerScale residual add with a saved branch).
+ * Rules as vggt_resid_scale_add_from with out == x. */
 int vggt_resid_scale_add(float* x, int64_t ldx, const void* branch, int bdtype, int64_t ldb, const float* gamma, int M,
                          int N, void* stream);
 
-/* out_f32[m, n] = x_f32[m, n] + gamma[n] * branch[m, n]  (out may equal x). */
+/* out_f32[m, n] = x_f32[m, n] + gamma[n] * branch[m, n]  (out may equal x).
+ * M == 0: VGGT_OK, nothing launched.  VGGT_ERR_SHAPE: M < 0, N < 1 or N % 4, out, x, branch or gamma
+ * NULL; VGGT_ERR_UNSUPPORTED: bdtype; VGGT_ERR_ALIGN: ldo, ldx or ldb % 4, out, x or gamma off 16
+ * bytes, branch off 8. */
 int vggt_resid_scale_add_from(float* out, int64_t ldo, const float* x, int64_t ldx, const void* branch, int bdtype,
                               int64_t ldb, const float* gamma, int M, int N, void* stream);
 
 /* dst[c, r] = src[r, c] for 2-byte elements; columns r in [rows, rows_pad) of dst are zero
- * (weight-gradient GEMM operands: dW = dY^T X as vggt_gemm_bf16(dY^T, X^T)). */
+ * (weight-gradient GEMM operands: dW = dY^T X as vggt_gemm_bf16(dY^T, X^T)).
+ * rows_pad == 0: VGGT_OK, nothing launched.  VGGT_ERR_SHAPE: rows < 0, cols < 1, rows_pad < rows, dst
+ * NULL, src NULL with rows > 0. */
 int vggt_transpose_b16(const void* src, int64_t lds, int rows, int cols, void* dst, int64_t ldd, int rows_pad,
                        void* stream);
 
 /* dW[n, k] (+)= bf16(sum_m dY[m, n] X[m, k]) for bf16 row-major dY [M, N], X [M, K] (the bf16-tier
  * Linear weight gradients, rounded like autocast's bf16 weight gradient): split-K over the token
  * dimension into fp32 partials in ws (>= vggt_wgrad_bf16_workspace_bytes), summed in split order.
- * N % 128 == 0, K % 128 == 0. */
+ * N % 128 == 0, K % 128 == 0.  VGGT_ERR_SHAPE: M, N or K < 1 (M == 0 included), N or K % 128, dy, x or dw
+ * NULL, ws NULL or too small; VGGT_ERR_ALIGN: ldy or ldx % 8, dy or x off 16 bytes. */
 size_t vggt_wgrad_bf16_workspace_bytes(int M, int N, int K);
 int vggt_wgrad_bf16(const void* dy, int64_t ldy, const void* x, int64_t ldx, int M, int N, int K, float* dw,
                     int64_t ldw, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
-/* dW[n, k] (+)= sum_m dY[m, n] X[m, k]  fp32 (skinny-M decoder / gated-update Linear weight gradients). */
+/* dW[n, k] (+)= sum_m dY[m, n] X[m, k]  fp32 (skinny-M decoder / gated-update Linear weight gradients).
+ * VGGT_ERR_SHAPE (the one error of this entry and the next): M, N or K < 1 (M == 0 included), N > 65535,
+ * dy, x, dw (or db) NULL. */
 int vggt_wgrad_f32(const float* dy, int64_t ldy, const float* x, int64_t ldx, int M, int N, int K, float* dw,
                    int64_t ldw, int accumulate, void* stream);
 /* The same and db[n] (+)= sum_m dY[m, n] in the one launch (LinearF32Fn backward: weight and bias gradients). */
@@ -1049,7 +1087,8 @@ int vggt_wgrad_bias_f32(const float* dy, int64_t ldy, const float* x, int64_t ld
                         int64_t ldw, float* db, int accumulate, void* stream);
 
 /* out[b] = sum_{i<n} a[b*bs + i] * c[b*bs + i]  (d chunk_scale of depth *= chunk_scale,
- * featureAligned_vggt.py:171, in training).  ws >= vggt_batch_dot_workspace_bytes(B, n). */
+ * featureAligned_vggt.py:171, in training).  ws >= vggt_batch_dot_workspace_bytes(B, n).
+ * VGGT_ERR_SHAPE (its one error): B or n < 1, a, c or out NULL, ws NULL or too small. */
 size_t vggt_batch_dot_workspace_bytes(int B, int64_t n);
 int vggt_batch_dot_f32(const float* a, const float* c, int64_t bs, int B, int64_t n, float* out, void* ws,
                        size_t ws_bytes, void* stream);

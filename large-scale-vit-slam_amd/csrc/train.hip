@@ -10,16 +10,16 @@
 // is deterministic: fixed row chunks write partial sums to a caller-provided
 // workspace, and a finalize pass adds the chunks in index order.
 #include <math.h>
-
 #include <stdlib.h>
+
+#include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 #include "mfma_frag.h"
 #include "norm_row.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f4;
 
 __device__ __forceinline__ void load4(const void* p, int dtype, int64_t off, float v[4]) {
   if (dtype == VGGT_DTYPE_BF16) {
@@ -29,7 +29,7 @@ __device__ __forceinline__ void load4(const void* p, int dtype, int64_t off, flo
     v[2] = bf2f(u.y & 0xffff);
     v[3] = bf2f(u.y >> 16);
   } else {
-    const f4 u = *(const f4*)((const float*)p + off);
+    const f32x4 u = *(const f32x4*)((const float*)p + off);
     v[0] = u[0];
     v[1] = u[1];
     v[2] = u[2];
@@ -43,8 +43,18 @@ __device__ __forceinline__ void store4(void* p, int dtype, int64_t off, const fl
     u.y = pack_bf2(v[2], v[3]);
     *(uint2*)((bf16_t*)p + off) = u;
   } else {
-    *(f4*)((float*)p + off) = f4{v[0], v[1], v[2], v[3]};
+    *(f32x4*)((float*)p + off) = f32x4{v[0], v[1], v[2], v[3]};
   }
+}
+// store o, round it to the stored dtype, add the stored values to s (a column sum of what was written)
+__device__ __forceinline__ void store4_sum(void* p, int dtype, int64_t off, float o[4], float s[4]) {
+  store4(p, dtype, off, o);
+  if (dtype == VGGT_DTYPE_BF16) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = round_bf(o[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s[j] += o[j];
 }
 
 // exact-erf GELU and its derivative (nn.GELU(approximate='none'))
@@ -59,35 +69,20 @@ __device__ __forceinline__ float gelu_d(float x) {
 // Block = 16 columns x 16 chunk slices: slice s sums chunks s, s+16, ...
 // (independent loads in flight), then the 16 slice sums are added in slice
 // order through LDS -- the same order on every run.
-__global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__ part, int nchunk, int n, int stride,
-                                                       float* __restrict__ out, int accumulate) {
-  __shared__ float red[16][17];
-  const int col = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int i = blockIdx.x * 16 + col;
-  float s = 0.f;
-  if (i < n) {
-#pragma unroll 4
-    for (int c = sl; c < nchunk; c += 16) s += part[(int64_t)c * stride + i];
-  }
-  red[sl][col] = s;
-  __syncthreads();
-  if (sl == 0 && i < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][col];
-    out[i] = accumulate ? out[i] + t : t;
-  }
-}
-
 // Up to four finalizes of one reduction (same chunk count and length, e.g.
-// a LayerNorm's weight and bias sums) in one launch: blockIdx.y = vector.
+// a LayerNorm's weight and bias sums) in one launch: blockIdx.y = job.
+struct FinJob {
+  const float* part;
+  int stride;
+  float* out;
+};
 struct FinJobs {
   const float* part[4];
   int stride[4];
   float* out[4];
 };
 
-__global__ __launch_bounds__(256) void finalize_multi_kernel(FinJobs jobs, int nchunk, int n, int accumulate) {
+__global__ __launch_bounds__(256) void finalize_kernel(FinJobs jobs, int nchunk, int n, int accumulate) {
   const int j = blockIdx.y;
   __shared__ float red[16][17];
   const float* __restrict__ part = jobs.part[j];
@@ -110,19 +105,18 @@ __global__ __launch_bounds__(256) void finalize_multi_kernel(FinJobs jobs, int n
   }
 }
 
-// queue the non-null (part, stride, out) triples as one finalize_multi launch
-static void finalize_many(hipStream_t s, int nchunk, int n, int accumulate, int count, const float* const* parts,
-                          const int* strides, float* const* outs) {
+// the one host path to finalize_kernel: the jobs with an output, as one launch
+void finalize_many(hipStream_t s, int nchunk, int n, int accumulate, std::initializer_list<FinJob> list) {
   FinJobs jobs{};
   int k = 0;
-  for (int a = 0; a < count; ++a)
-    if (outs[a]) {
-      jobs.part[k] = parts[a];
-      jobs.stride[k] = strides[a];
-      jobs.out[k] = outs[a];
+  for (const FinJob& j : list)
+    if (j.out) {
+      jobs.part[k] = j.part;
+      jobs.stride[k] = j.stride;
+      jobs.out[k] = j.out;
       ++k;
     }
-  if (k) finalize_multi_kernel<<<dim3((n + 15) / 16, k), 256, 0, s>>>(jobs, nchunk, n, accumulate);
+  if (k) finalize_kernel<<<dim3((n + 15) / 16, k), 256, 0, s>>>(jobs, nchunk, n, accumulate);
 }
 
 // ------------------------------------------------------------ column sums
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(256) void colred_kernel(const void* a, int adt, int
   float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
   float g[4] = {1.f, 1.f, 1.f, 1.f};
   if (MODE == 1) {
-    const f4 gv = *(const f4*)(gamma + c0);
+    const f32x4 gv = *(const f32x4*)(gamma + c0);
     g[0] = gv[0];
     g[1] = gv[1];
     g[2] = gv[2];
@@ -168,32 +162,20 @@ __global__ __launch_bounds__(256) void colred_kernel(const void* a, int adt, int
         s0[j] += av[j] * bv[j];
         o[j] = g[j] * av[j];
       }
-      store4(out, odt, (int64_t)r * ldo + c0, o);
-      if (odt == VGGT_DTYPE_BF16) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = round_bf(o[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s1[j] += o[j];
+      store4_sum(out, odt, (int64_t)r * ldo + c0, o, s1);
     } else {
       float bv[4], o[4];
       load4(b, bdt, (int64_t)r * ldb + c0, bv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = av[j] * gelu_d(bv[j]);
-      store4(out, odt, (int64_t)r * ldo + c0, o);
-      if (odt == VGGT_DTYPE_BF16) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = round_bf(o[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s0[j] += o[j];
+      store4_sum(out, odt, (int64_t)r * ldo + c0, o, s0);
     }
   }
   float* p0 = part + (int64_t)blockIdx.y * N + c0;
-  *(f4*)p0 = f4{s0[0], s0[1], s0[2], s0[3]};
+  *(f32x4*)p0 = f32x4{s0[0], s0[1], s0[2], s0[3]};
   if (MODE == 1) {
     float* p1 = part + ((int64_t)gridDim.y + blockIdx.y) * N + c0;
-    *(f4*)p1 = f4{s1[0], s1[1], s1[2], s1[3]};
+    *(f32x4*)p1 = f32x4{s1[0], s1[1], s1[2], s1[3]};
   }
 }
 
@@ -218,11 +200,11 @@ __global__ __launch_bounds__(256) void ew_kernel(const void* x, int xdt, int64_t
     float br[4], acc[4];
     load4(y, ydt, (int64_t)r * ldy + c, br);
     float* xp = (float*)x + (int64_t)r * ldx + c;
-    const f4 xv = *(const f4*)(src + (int64_t)r * lds + c);
-    const f4 gv = *(const f4*)(gamma + c);
+    const f32x4 xv = *(const f32x4*)(src + (int64_t)r * lds + c);
+    const f32x4 gv = *(const f32x4*)(gamma + c);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = xv[j] + gv[j] * br[j];
-    *(f4*)xp = f4{acc[0], acc[1], acc[2], acc[3]};
+    *(f32x4*)xp = f32x4{acc[0], acc[1], acc[2], acc[3]};
   }
 }
 
@@ -332,13 +314,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ x,
   }
 }
 
-template <int NV>
-void launch_ln_bwd(const void* x, int xdt, int64_t ldx, const float* w, float eps, const void* dy, int ydt,
-                   int64_t ldy, void* dx, int dxdt, int64_t lddx, int acc, int M, RowMap rm, int nblk, int rpb,
-                   float* part, hipStream_t s) {
-  ln_bwd_kernel<NV><<<nblk, 256, 0, s>>>(x, xdt, ldx, w, eps, dy, ydt, ldy, dx, dxdt, lddx, acc, M, rm, rpb, part);
-}
-
 // ------------------------------------------------------------ per-head norm + RoPE backward
 // Forward (norm.hip headnorm_rope_kernel / small.hip f32 variant): for head h
 // of row m, u = pre-norm values, xhat = LN(u), y = xhat*w + b, z = rope(y).
@@ -347,6 +322,16 @@ void launch_ln_bwd(const void* x, int xdt, int64_t ldx, const float* w, float ep
 // the head's D values.  du overwrites dz in place.  Heads [0, hsplit) belong
 // to weight set 0 (q_norm), the rest to set 1 (k_norm); parameter partials
 // part[blk][set][w|b][D].
+//
+// head_sum: butterfly over the LPH consecutive lanes of a head.  Not hn_head_sum of common.h: for
+// 64-wide heads that one adds in the forward GEMM epilogue's order, another rounding of the statistics.
+template <int LPH>
+__device__ __forceinline__ float head_sum(float s) {
+#pragma unroll
+  for (int o = 1; o < LPH; o <<= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
 template <int D, int MODE, int DT>
 __global__ __launch_bounds__(256) void headnorm_rope_bwd_kernel(const void* __restrict__ pre, int64_t ldp,
                                                                 void* __restrict__ grad, int64_t ldg, int M, int H,
@@ -418,18 +403,14 @@ __global__ __launch_bounds__(256) void headnorm_rope_bwd_kernel(const void* __re
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += u[j];
-#pragma unroll
-        for (int o = 1; o < LPH; o <<= 1) s += __shfl_xor(s, o, 64);
-        const float mean = s * (1.f / D);
+        const float mean = head_sum<LPH>(s) * (1.f / D);
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float d = u[j] - mean;
           q += d * d;
         }
-#pragma unroll
-        for (int o = 1; o < LPH; o <<= 1) q += __shfl_xor(q, o, 64);
-        const float rstd = rsqrtf(q * (1.f / D) + eps);
+        const float rstd = rsqrtf(head_sum<LPH>(q) * (1.f / D) + eps);
         float s1 = 0.f, s2 = 0.f, xh[8], gd[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -438,12 +419,7 @@ __global__ __launch_bounds__(256) void headnorm_rope_bwd_kernel(const void* __re
           s1 += gd[j];
           s2 += gd[j] * xh[j];
         }
-#pragma unroll
-        for (int o = 1; o < LPH; o <<= 1) {
-          s1 += __shfl_xor(s1, o, 64);
-          s2 += __shfl_xor(s2, o, 64);
-        }
-        const float m1 = s1 * (1.f / D), m2 = s2 * (1.f / D);
+        const float m1 = head_sum<LPH>(s1) * (1.f / D), m2 = head_sum<LPH>(s2) * (1.f / D);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           du[j] = rstd * (gd[j] - m1 - xh[j] * m2);
@@ -520,7 +496,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(
             f[2 * t + 1] = bf2f((bf16_t)(w4[t] >> 16));
           }
         } else {
-          const f4 a0 = *(const f4*)((const float*)base + off), a1 = *(const f4*)((const float*)base + off + 4);
+          const f32x4 a0 = *(const f32x4*)((const float*)base + off), a1 = *(const f32x4*)((const float*)base + off + 4);
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             f[t] = a0[t];
@@ -575,51 +551,45 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(
     scores(0.0);
   __syncthreads();
   // a thread per query row; P ends in sdp's slot for dv, dS in sp's
-  for (int r = tid; r < nq; r += 256) {
-    float* pr = sp + r * nk;
-    float* dr = sdp + r * nk;
-    float m = -INFINITY;
-    for (int c = 0; c < nk; ++c) m = fmaxf(m, pr[c]);
-    if (bf) {
-      float l = 0.f;
+  auto softmax = [&](auto zero) {
+    using acc_t = decltype(zero);
+    constexpr bool fast = std::is_same<acc_t, float>::value;  // fast exponential, reciprocal multiply
+    for (int r = tid; r < nq; r += 256) {
+      float* pr = sp + r * nk;
+      float* dr = sdp + r * nk;
+      float m = -INFINITY;
+      for (int c = 0; c < nk; ++c) m = fmaxf(m, pr[c]);
+      acc_t l = zero;
       for (int c = 0; c < nk; ++c) {
-        const float e = __expf(pr[c] - m);
+        float e;
+        if constexpr (fast)
+          e = __expf(pr[c] - m);
+        else
+          e = expf(pr[c] - m);
         pr[c] = e;
-        l += e;
+        l += (acc_t)e;
       }
-      const float inv = 1.f / l;
-      float delta = 0.f;
+      const float lf = (float)l, inv = 1.f / lf;
+      acc_t delta = zero;
       for (int c = 0; c < nk; ++c) {
-        pr[c] *= inv;
-        delta += pr[c] * dr[c];
+        if constexpr (fast)
+          pr[c] *= inv;
+        else
+          pr[c] /= lf;
+        delta += (acc_t)pr[c] * (acc_t)dr[c];
       }
       for (int c = 0; c < nk; ++c) {
         const float p = pr[c];
-        const float ds = p * (dr[c] - delta);
-        dr[c] = p;
-        pr[c] = ds;
-      }
-    } else {
-      double l = 0.0;
-      for (int c = 0; c < nk; ++c) {
-        const float e = expf(pr[c] - m);
-        pr[c] = e;
-        l += (double)e;
-      }
-      const float lf = (float)l;
-      double delta = 0.0;
-      for (int c = 0; c < nk; ++c) {
-        pr[c] /= lf;
-        delta += (double)pr[c] * (double)dr[c];
-      }
-      for (int c = 0; c < nk; ++c) {
-        const float p = pr[c];
-        const float ds = (float)((double)p * ((double)dr[c] - delta));
+        const float ds = (float)((acc_t)p * ((acc_t)dr[c] - delta));
         dr[c] = p;
         pr[c] = ds;
       }
     }
-  }
+  };
+  if (bf)
+    softmax(0.f);
+  else
+    softmax(0.0);
   __syncthreads();
   auto st2 = [&](void* base, int64_t off, float a0, float a1) {
     if (bf) {
@@ -701,6 +671,53 @@ __global__ __launch_bounds__(256) void batch_dot_kernel(const float* __restrict_
 // permutation on A and B).  128x128 output tile per workgroup, 4 waves x
 // (64 x 64), double-buffered LDS, register-staged loads of tile t+1 in
 // flight during tile t's MFMAs.
+//
+// What the register-staged and the LDS-DMA kernel share, first.  A workgroup's 128 x 128 tile of dW
+// with its token split [mb, me), and the 64 x 64 quadrant (wn, wk) of the tile that `wave` owns:
+struct WgradTile {
+  int n0, k0, mb, me, wn, wk;
+  __device__ __forceinline__ WgradTile(int wave, int M, int N, int mchunk) {
+    const int ntn = N / 128;
+    n0 = (blockIdx.x % ntn) * 128, k0 = (blockIdx.x / ntn) * 128;
+    mb = blockIdx.y * mchunk, me = min(M, mb + mchunk);
+    wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
+  }
+};
+// one staged pair of [32 m][128] tiles (ty: dY, tx: X): 2 k-steps x (2 x 2) MFMAs into the wave's quadrant
+__device__ __forceinline__ void wgrad_mfma_step(const char* ty, const char* tx, const WgradTile& wt, int lane,
+                                                f32x16 (&acc)[2][2]) {
+  using namespace vggt_frag;
+#pragma unroll
+  for (int ss = 0; ss < 2; ++ss) {
+    bf16x8 af[2], bfr[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      af[i] = trfrag<128>(ty, (wt.wn >> 5) + i, 0, ss, lane);
+      bfr[i] = trfrag<128>(tx, (wt.wk >> 5) + i, 0, ss, lane);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+  }
+}
+// part[split][n][k] = the wave's accumulators
+__device__ __forceinline__ void wgrad_store_partials(float* __restrict__ part, int N, int K, const WgradTile& wt,
+                                                     int lane, const f32x16 (&acc)[2][2]) {
+  const int hl = lane >> 5;
+  float* pz = part + (int64_t)blockIdx.y * N * K;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = wt.n0 + wt.wn + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hl;
+        const int k = wt.k0 + wt.wk + 32 * j + (lane & 31);
+        pz[(int64_t)n * K + k] = acc[i][j][r];
+      }
+}
+
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const bf16_t* __restrict__ dy, int64_t ldy,
                                                          const bf16_t* __restrict__ x, int64_t ldx, int M, int N,
                                                          int K, int mchunk, float* __restrict__ part) {
@@ -708,16 +725,10 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const bf16_t* __restric
   constexpr int ROWP = Geo<128>::ROWP;
   constexpr int TB = 32 * ROWP;
   __shared__ __attribute__((aligned(16))) char smem[2][2 * TB];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ntn = N / 128;
-  const int n0 = (blockIdx.x % ntn) * 128, k0 = (blockIdx.x / ntn) * 128;
-  const int mb = blockIdx.y * mchunk, me = min(M, mb + mchunk);
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
+  const int lane = threadIdx.x & 63;
+  const WgradTile wt(threadIdx.x >> 6, M, N, mchunk);
+  const int n0 = wt.n0, k0 = wt.k0, mb = wt.mb, me = wt.me;
+  f32x16 acc[2][2] = {};
   // staging: 512 16-B chunks per operand tile; thread t moves chunks t and t+256
   uint4 ry[2], rx[2];
   auto load = [&](int m0) {
@@ -746,34 +757,11 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const bf16_t* __restric
     if (t + 1 < nt) load(mb + (t + 1) * 32);
     const char* ty = smem[cur];
     const char* tx = smem[cur] + TB;
-#pragma unroll
-    for (int ss = 0; ss < 2; ++ss) {
-      bf16x8 af[2], bfr[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        af[i] = trfrag<128>(ty, (wn >> 5) + i, 0, ss, lane);
-        bfr[i] = trfrag<128>(tx, (wk >> 5) + i, 0, ss, lane);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    wgrad_mfma_step(ty, tx, wt, lane, acc);
     if (t + 1 < nt) store(cur ^ 1);
     __syncthreads();
   }
-  const int hl = lane >> 5;
-  float* pz = part + (int64_t)blockIdx.y * N * K;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        const int k = k0 + wk + 32 * j + (lane & 31);
-        pz[(int64_t)n * K + k] = acc[i][j][r];
-      }
+  wgrad_store_partials(part, N, K, wt, lane, acc);
 }
 
 // The same product with the token tiles staged by LDS-DMA (buffer_load ... lds)
@@ -816,10 +804,8 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const bf16_t* __restrict
   extern __shared__ __attribute__((aligned(16))) char wsm[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ntn = N / 128;
-  const int n0 = (blockIdx.x % ntn) * 128, k0 = (blockIdx.x / ntn) * 128;
-  const int mb = blockIdx.y * mchunk, me = min(M, mb + mchunk);
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
+  const WgradTile wt(wave, M, N, mchunk);
+  const int n0 = wt.n0, k0 = wt.k0, mb = wt.mb, me = wt.me;
   // waves 0-1 stage the dY tile, waves 2-3 the X tile, 5 pieces each:
   // piece p = 5 (wave & 1) + i of operand wave >> 1
   const bool xo = wave >= 2;
@@ -848,11 +834,7 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int i = 0; i < 5; ++i) wg_dma16(rs, voff[i], 0u, b + i * 1024);
   };
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
+  f32x16 acc[2][2] = {};
   const int nt = (me - mb + 31) / 32;  // >= 1: the host never launches an empty split
   stage(0, 0);
   stage(1, 1);
@@ -865,36 +847,13 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const bf16_t* __restrict
     stage(s2, t + 2);
     const char* ty = wsm + slot * WG_SLOT;
     const char* tx = ty + WG_TILE;
-#pragma unroll
-    for (int ss = 0; ss < 2; ++ss) {
-      bf16x8 af[2], bfr[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        af[i] = trfrag<128>(ty, (wn >> 5) + i, 0, ss, lane);
-        bfr[i] = trfrag<128>(tx, (wk >> 5) + i, 0, ss, lane);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    wgrad_mfma_step(ty, tx, wt, lane, acc);
     // tile t+1 landed (its 5 pieces are older than tile t+2's 5), reads of slot done
     asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     slot = slot == 2 ? 0 : slot + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the surplus DMA before the workgroup ends
-  const int hl = lane >> 5;
-  float* pz = part + (int64_t)blockIdx.y * N * K;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        const int k = k0 + wk + 32 * j + (lane & 31);
-        pz[(int64_t)n * K + k] = acc[i][j][r];
-      }
+  wgrad_store_partials(part, N, K, wt, lane, acc);
 }
 
 // out[n][k] (+)= round_bf16(sum_z part[z][n][k])  (fixed split order)
@@ -910,99 +869,154 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   *o = accumulate ? *o + s : s;
 }
 
-int nchunks_for(int M, int maxc, int rows = 64) {
-  int c = (M + rows - 1) / rows;
-  return c < 1 ? 1 : (c > maxc ? maxc : c);
+// ------------------------------------------------------------ host: chunk plan, argument check, launchers
+// Row chunking of a deterministic reduction: M rows (elements, for vggt_batch_dot_f32) in nchunk <= maxc chunks of
+// `rows` each (at least min_rows while the cap allows).  A chunk writes one partial per reduced vector; vector i
+// of `width` floats per chunk starts vec(i, width) floats into the workspace.  Every entry and its
+// *_workspace_bytes function take their numbers from here.
+struct ChunkPlan {
+  int nchunk;
+  int64_t rows;
+  size_t vec(int i, size_t width) const { return (size_t)i * nchunk * width; }
+  size_t bytes(int nvec, size_t width) const { return vec(nvec, width) * sizeof(float); }
+};
+ChunkPlan chunk_plan(int64_t M, int maxc, int min_rows) {
+  int64_t c = (M + min_rows - 1) / min_rows;
+  c = c < 1 ? 1 : (c > maxc ? maxc : c);
+  return {(int)c, (M + c - 1) / c};
 }
-// Row chunking of the column reductions / row-wise backward kernels: enough
-// workgroups (up to ~4 per CU) that the serial per-row loads of each wave
-// overlap across waves; more chunks only add fp32 partials (<= 8 MB).
+// Column reductions / row-wise backward kernels: enough workgroups (up to ~4 per CU) that the serial per-row
+// loads of each wave overlap across waves; more chunks only add fp32 partials (<= 8 MB).
 constexpr int COLRED_MAXC = 1024, COLRED_ROWS = 16;
 constexpr int ROWBWD_MAXC = 2048, ROWBWD_ROWS = 16;
+constexpr int BATCH_DOT_MAXC = 256, BATCH_DOT_ELEMS = 65536;
+
+// One matrix argument as its kernel touches it: rows of ld elements (a multiple of ld_mult; 0 for a vector), the
+// base aligned to `align` bytes, elements VGGT_DTYPE_F32 or VGGT_DTYPE_BF16, NULL allowed or not.
+struct Mat {
+  const void* p = nullptr;
+  int dtype = VGGT_DTYPE_F32;
+  int64_t ld = 0;
+  int ld_mult = 1;
+  int align = 1;
+  bool nullable = false;
+  void* out() const { return const_cast<void*>(p); }
+};
+constexpr Mat NO_MAT{nullptr, VGGT_DTYPE_F32, 0, 1, 1, true};
+
+// The one answer for an entry's matrices, before anything is launched: a missing required pointer is
+// VGGT_ERR_SHAPE, a dtype code other than the two VGGT_ERR_UNSUPPORTED, a leading dimension or a base off its
+// alignment VGGT_ERR_ALIGN.
+int check_mats(std::initializer_list<Mat> mats) {
+  for (const Mat& m : mats)
+    if (!m.p && !m.nullable) return VGGT_ERR_SHAPE;
+  for (const Mat& m : mats)
+    if (m.dtype != VGGT_DTYPE_F32 && m.dtype != VGGT_DTYPE_BF16) return VGGT_ERR_UNSUPPORTED;
+  for (const Mat& m : mats)
+    if (m.ld % m.ld_mult || (uintptr_t)m.p % m.align) return VGGT_ERR_ALIGN;
+  return VGGT_OK;
+}
+
+// vggt_colsum / vggt_layerscale_bwd / vggt_gelu_bwd: colred_kernel<MODE> over the plan's chunks, then
+// sum0 (+)= the chunks' first partial vector and (MODE 1) sum1 += their second.
+template <int MODE>
+int colred(Mat a, Mat b, const float* gamma, Mat out, int M, int N, float* sum0, float* sum1, int accumulate, void* ws,
+           size_t ws_bytes, void* stream) {
+  if (M <= 0 || N <= 0 || N % 4) return VGGT_ERR_SHAPE;
+  const Mat g{gamma, VGGT_DTYPE_F32, 0, 1, 16, MODE != 1}, s0{sum0, VGGT_DTYPE_F32, 0, 1, 1, MODE != 0};
+  if (int rc = check_mats({a, b, out, g, s0})) return rc;
+  const ChunkPlan plan = chunk_plan(M, COLRED_MAXC, COLRED_ROWS);
+  if (!ws || ws_bytes < plan.bytes(MODE == 1 ? 2 : 1, N)) return VGGT_ERR_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)ws;
+  colred_kernel<MODE><<<dim3((N / 4 + 255) / 256, plan.nchunk), 256, 0, s>>>(
+      a.p, a.dtype, a.ld, b.p, b.dtype, b.ld, gamma, out.out(), out.dtype, out.ld, M, N, (int)plan.rows, part);
+  finalize_many(s, plan.nchunk, N, accumulate, {{part, N, sum0}, {part + plan.vec(1, N), N, sum1}});
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+// vggt_gelu_fwd (MODE 0: y = GELU(x)) / vggt_resid_scale_add_from (MODE 1: x = src + gamma * y)
+template <int MODE>
+int elementwise(Mat x, Mat y, const float* gamma, Mat src, int M, int N, void* stream) {
+  if (M <= 0 || N <= 0 || N % 4) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
+  if (int rc = check_mats({x, y, src, {gamma, VGGT_DTYPE_F32, 0, 1, 16, MODE != 1}})) return rc;
+  const int64_t nv = (int64_t)M * N / 4;
+  ew_kernel<MODE><<<(unsigned)((nv + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      x.p, x.dtype, x.ld, y.out(), y.dtype, y.ld, gamma, M, N, (const float*)src.p, src.ld);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+// vggt_wgrad_f32 (db == NULL) / vggt_wgrad_bias_f32: the bias is one more column of the grid
+int wgrad_f32(const float* dy, int64_t ldy, const float* x, int64_t ldx, int M, int N, int K, float* dw, int64_t ldw,
+              int accumulate, float* db, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || N > 65535) return VGGT_ERR_SHAPE;
+  if (int rc = check_mats({{dy}, {x}, {dw}})) return rc;
+  dim3 grid((K + (db ? 1 : 0) + 255) / 256, N);
+  wgrad_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dy, ldy, x, ldx, M, N, K, dw, ldw, accumulate, db);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+using ln_bwd_kernel_t = decltype(&ln_bwd_kernel<1>);
+ln_bwd_kernel_t ln_bwd_kernel_for(int C) {
+  switch (C) {
+    case 256: return ln_bwd_kernel<1>;
+    case 512: return ln_bwd_kernel<2>;
+    case 1024: return ln_bwd_kernel<4>;
+    default: return nullptr;
+  }
+}
+
+using hnrb_kernel_t = decltype(&headnorm_rope_bwd_kernel<64, VGGT_ROPE_NONE, VGGT_DTYPE_F32>);
+
+template <int D, int DT>
+hnrb_kernel_t hnrb_kernel(int mode) {
+  switch (mode) {
+    case VGGT_ROPE_NONE: return headnorm_rope_bwd_kernel<D, VGGT_ROPE_NONE, DT>;
+    case VGGT_ROPE_2D: return headnorm_rope_bwd_kernel<D, VGGT_ROPE_2D, DT>;
+    case VGGT_ROPE_1D: return headnorm_rope_bwd_kernel<D, VGGT_ROPE_1D, DT>;
+    default: return nullptr;
+  }
+}
 
 }  // namespace
 
 // ============================================================ C ABI
 extern "C" size_t vggt_colred_workspace_bytes(int M, int N) {
-  return (size_t)2 * nchunks_for(M, COLRED_MAXC, COLRED_ROWS) * (size_t)N * sizeof(float);
+  return chunk_plan(M, COLRED_MAXC, COLRED_ROWS).bytes(2, N);
 }
 
 extern "C" int vggt_colsum(const void* x, int dtype, int64_t ldx, int M, int N, float* out, int accumulate, void* ws,
                            size_t ws_bytes, void* stream) {
-  if (M <= 0 || N <= 0 || N % 4) return VGGT_ERR_SHAPE;
-  if (dtype != VGGT_DTYPE_F32 && dtype != VGGT_DTYPE_BF16) return VGGT_ERR_UNSUPPORTED;
-  if (ldx % 4 || (uintptr_t)x % 8) return VGGT_ERR_ALIGN;
-  const int nc = nchunks_for(M, COLRED_MAXC, COLRED_ROWS);
-  if (!ws || ws_bytes < (size_t)nc * N * sizeof(float)) return VGGT_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpc = (M + nc - 1) / nc;
-  dim3 grid((N / 4 + 255) / 256, nc);
-  colred_kernel<0><<<grid, 256, 0, s>>>(x, dtype, ldx, nullptr, 0, 0, nullptr, nullptr, 0, 0, M, N, rpc, (float*)ws);
-  finalize_kernel<<<(N + 15) / 16, 256, 0, s>>>((const float*)ws, nc, N, N, out, accumulate);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return colred<0>({x, dtype, ldx, 4, 8}, NO_MAT, nullptr, NO_MAT, M, N, out, nullptr, accumulate, ws, ws_bytes,
+                   stream);
 }
 
 extern "C" int vggt_layerscale_bwd(const float* dout, int64_t ldd, const void* branch, int bdtype, int64_t ldb,
                                    const float* gamma, void* dbranch, int odtype, int64_t ldo, int M, int N,
                                    float* dgamma, float* dbias, void* ws, size_t ws_bytes, void* stream) {
-  if (M <= 0 || N <= 0 || N % 4) return VGGT_ERR_SHAPE;
-  if ((ldd | ldb | ldo) % 4 || ((uintptr_t)dout | (uintptr_t)gamma) % 16 || ((uintptr_t)branch | (uintptr_t)dbranch) % 8)
-    return VGGT_ERR_ALIGN;
-  const int nc = nchunks_for(M, COLRED_MAXC, COLRED_ROWS);
-  if (!ws || ws_bytes < (size_t)2 * nc * N * sizeof(float)) return VGGT_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpc = (M + nc - 1) / nc;
-  dim3 grid((N / 4 + 255) / 256, nc);
-  colred_kernel<1><<<grid, 256, 0, s>>>(dout, VGGT_DTYPE_F32, ldd, branch, bdtype, ldb, gamma, dbranch, odtype, ldo,
-                                        M, N, rpc, (float*)ws);
-  const float* parts[2] = {(const float*)ws, (const float*)ws + (size_t)nc * N};
-  const int strides[2] = {N, N};
-  float* outs[2] = {dgamma, dbias};
-  finalize_many(s, nc, N, 1, 2, parts, strides, outs);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return colred<1>({dout, VGGT_DTYPE_F32, ldd, 4, 16}, {branch, bdtype, ldb, 4, 8}, gamma, {dbranch, odtype, ldo, 4, 8},
+                   M, N, dgamma, dbias, 1, ws, ws_bytes, stream);
 }
 
 extern "C" int vggt_gelu_fwd(const void* x, int xdtype, int64_t ldx, void* y, int ydtype, int64_t ldy, int M, int N,
                              void* stream) {
-  if (M <= 0 || N <= 0 || N % 4) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if ((ldx | ldy) % 4 || ((uintptr_t)x | (uintptr_t)y) % 8) return VGGT_ERR_ALIGN;
-  const int64_t nv = (int64_t)M * N / 4;
-  ew_kernel<0><<<(unsigned)((nv + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, xdtype, ldx, y, ydtype, ldy, nullptr,
-                                                                               M, N);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return elementwise<0>({x, xdtype, ldx, 4, 8}, {y, ydtype, ldy, 4, 8}, nullptr, NO_MAT, M, N, stream);
 }
 
 extern "C" int vggt_gelu_bwd(const void* dh, int dhdtype, int64_t lddh, const void* pre, int predtype, int64_t ldp,
                              void* dpre, int odtype, int64_t ldo, int M, int N, float* dbias, void* ws,
                              size_t ws_bytes, void* stream) {
-  if (M <= 0 || N <= 0 || N % 4) return VGGT_ERR_SHAPE;
-  if ((lddh | ldp | ldo) % 4 || ((uintptr_t)dh | (uintptr_t)pre | (uintptr_t)dpre) % 8) return VGGT_ERR_ALIGN;
-  const int nc = nchunks_for(M, COLRED_MAXC, COLRED_ROWS);
-  if (!ws || ws_bytes < (size_t)nc * N * sizeof(float)) return VGGT_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpc = (M + nc - 1) / nc;
-  dim3 grid((N / 4 + 255) / 256, nc);
-  colred_kernel<2><<<grid, 256, 0, s>>>(dh, dhdtype, lddh, pre, predtype, ldp, nullptr, dpre, odtype, ldo, M, N, rpc,
-                                        (float*)ws);
-  if (dbias) finalize_kernel<<<(N + 15) / 16, 256, 0, s>>>((const float*)ws, nc, N, N, dbias, 1);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return colred<2>({dh, dhdtype, lddh, 4, 8}, {pre, predtype, ldp, 4, 8}, nullptr, {dpre, odtype, ldo, 4, 8}, M, N,
+                   dbias, nullptr, 1, ws, ws_bytes, stream);
 }
 
 extern "C" int vggt_resid_scale_add_from(float* out, int64_t ldo, const float* x, int64_t ldx, const void* branch,
                                          int bdtype, int64_t ldb, const float* gamma, int M, int N, void* stream) {
-  if (M <= 0 || N <= 0 || N % 4) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if ((ldo | ldx | ldb) % 4 || (uintptr_t)out % 16 || (uintptr_t)x % 16 || (uintptr_t)gamma % 16 ||
-      (uintptr_t)branch % 8)
-    return VGGT_ERR_ALIGN;
-  const int64_t nv = (int64_t)M * N / 4;
-  ew_kernel<1><<<(unsigned)((nv + 255) / 256), 256, 0, (hipStream_t)stream>>>(out, VGGT_DTYPE_F32, ldo, (void*)branch,
-                                                                               bdtype, ldb, gamma, M, N, x, ldx);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return elementwise<1>({out, VGGT_DTYPE_F32, ldo, 4, 16}, {branch, bdtype, ldb, 4, 8}, gamma,
+                        {x, VGGT_DTYPE_F32, ldx, 4, 16}, M, N, stream);
 }
 
 extern "C" int vggt_resid_scale_add(float* x, int64_t ldx, const void* branch, int bdtype, int64_t ldb,
@@ -1014,6 +1028,7 @@ extern "C" int vggt_transpose_b16(const void* src, int64_t lds, int rows, int co
                                   int rows_pad, void* stream) {
   if (rows < 0 || cols <= 0 || rows_pad < rows) return VGGT_ERR_SHAPE;
   if (rows_pad == 0) return VGGT_OK;
+  if (int rc = check_mats({{src, VGGT_DTYPE_F32, 0, 1, 1, rows == 0}, {dst}})) return rc;
   dim3 grid((cols + 63) / 64, (rows_pad + 63) / 64);
   transpose_b16_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const uint16_t*)src, lds, rows, cols, (uint16_t*)dst,
                                                               ldd, rows_pad);
@@ -1022,7 +1037,7 @@ extern "C" int vggt_transpose_b16(const void* src, int64_t lds, int rows, int co
 }
 
 extern "C" size_t vggt_layernorm_bwd_workspace_bytes(int M, int C) {
-  return (size_t)2 * nchunks_for(M, ROWBWD_MAXC, ROWBWD_ROWS) * (size_t)C * sizeof(float);
+  return chunk_plan(M, ROWBWD_MAXC, ROWBWD_ROWS).bytes(2, C);
 }
 
 extern "C" int vggt_layernorm_bwd(const void* x, int xdtype, int64_t ldx, const float* w, float eps, const void* dy,
@@ -1030,37 +1045,28 @@ extern "C" int vggt_layernorm_bwd(const void* x, int xdtype, int64_t ldx, const 
                                   int C, int group, int x_group_stride, int x_row_offset, int y_group_stride,
                                   int y_row_offset, float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
   if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (C % 256 || C > 1024 || group <= 0) return VGGT_ERR_SHAPE;
+  const ln_bwd_kernel_t k = ln_bwd_kernel_for(C);
+  if (!k || group <= 0) return VGGT_ERR_SHAPE;
   if (accumulate & ~(VGGT_LN_BWD_DX_ACCUMULATE | VGGT_LN_BWD_PARAMS_WRITE)) return VGGT_ERR_UNSUPPORTED;
   const int param_acc = (accumulate & VGGT_LN_BWD_PARAMS_WRITE) ? 0 : 1;
   accumulate &= VGGT_LN_BWD_DX_ACCUMULATE;
+  if (int rc = check_mats({{x, xdtype, ldx, 4, 8}, {dy, dydtype, ldy, 4, 8}, {dx, dxdtype, lddx, 4, 8}})) return rc;
   if (accumulate && dxdtype != VGGT_DTYPE_F32) return VGGT_ERR_UNSUPPORTED;
-  if ((ldx | ldy | lddx) % 4 || ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 8) return VGGT_ERR_ALIGN;
-  const int nblk = nchunks_for(M, ROWBWD_MAXC, ROWBWD_ROWS);
+  const ChunkPlan plan = chunk_plan(M, ROWBWD_MAXC, ROWBWD_ROWS);
   const bool want = dw || db;
-  if (want && (!ws || ws_bytes < (size_t)2 * nblk * C * sizeof(float))) return VGGT_ERR_SHAPE;
-  const int rpb = (M + nblk - 1) / nblk;
+  if (want && (!ws || ws_bytes < plan.bytes(2, C))) return VGGT_ERR_SHAPE;
   RowMap rm{group, x_group_stride, x_row_offset, y_group_stride, y_row_offset};
   hipStream_t s = (hipStream_t)stream;
   float* part = want ? (float*)ws : nullptr;
-  switch (C / 256) {
-    case 1: launch_ln_bwd<1>(x, xdtype, ldx, w, eps, dy, dydtype, ldy, dx, dxdtype, lddx, accumulate, M, rm, nblk, rpb, part, s); break;
-    case 2: launch_ln_bwd<2>(x, xdtype, ldx, w, eps, dy, dydtype, ldy, dx, dxdtype, lddx, accumulate, M, rm, nblk, rpb, part, s); break;
-    case 4: launch_ln_bwd<4>(x, xdtype, ldx, w, eps, dy, dydtype, ldy, dx, dxdtype, lddx, accumulate, M, rm, nblk, rpb, part, s); break;
-    default: return VGGT_ERR_SHAPE;
-  }
-  if (want) {
-    const float* parts[2] = {part, part + (size_t)nblk * C};
-    const int strides[2] = {C, C};
-    float* outs[2] = {dw, db};
-    finalize_many(s, nblk, C, param_acc, 2, parts, strides, outs);
-  }
+  k<<<plan.nchunk, 256, 0, s>>>(x, xdtype, ldx, w, eps, dy, dydtype, ldy, dx, dxdtype, lddx, accumulate, M, rm,
+                                (int)plan.rows, part);
+  if (want) finalize_many(s, plan.nchunk, C, param_acc, {{part, C, dw}, {part + plan.vec(1, C), C, db}});
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
 
 extern "C" size_t vggt_headnorm_rope_bwd_workspace_bytes(int M, int D) {
-  return (size_t)4 * nchunks_for(M, ROWBWD_MAXC, ROWBWD_ROWS) * (size_t)D * sizeof(float);
+  return chunk_plan(M, ROWBWD_MAXC, ROWBWD_ROWS).bytes(4, D);
 }
 
 extern "C" int vggt_headnorm_rope_bwd(const void* pre, int64_t ldp, void* grad, int64_t ldg, int dtype, int M, int H,
@@ -1070,40 +1076,25 @@ extern "C" int vggt_headnorm_rope_bwd(const void* pre, int64_t ldp, void* grad, 
                                       size_t ws_bytes, void* stream) {
   if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
   if (H <= 0 || (D != 64 && D != 128) || hsplit < 0 || hsplit > H) return VGGT_ERR_SHAPE;
-  if (dtype != VGGT_DTYPE_F32 && dtype != VGGT_DTYPE_BF16) return VGGT_ERR_UNSUPPORTED;
-  if ((ldp | ldg) % 8 || ((uintptr_t)pre | (uintptr_t)grad) % 16) return VGGT_ERR_ALIGN;
+  if (int rc = check_mats({{pre, dtype, ldp, 8, 16}, {grad, dtype, ldg, 8, 16}})) return rc;
   if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
     return VGGT_ERR_SHAPE;
-  const int nblk = nchunks_for(M, ROWBWD_MAXC, ROWBWD_ROWS);
+  const bool bf = dtype == VGGT_DTYPE_BF16;
+  const hnrb_kernel_t k =
+      D == 64 ? (bf ? hnrb_kernel<64, VGGT_DTYPE_BF16>(rope_mode) : hnrb_kernel<64, VGGT_DTYPE_F32>(rope_mode))
+              : (bf ? hnrb_kernel<128, VGGT_DTYPE_BF16>(rope_mode) : hnrb_kernel<128, VGGT_DTYPE_F32>(rope_mode));
+  if (!k) return VGGT_ERR_UNSUPPORTED;
+  const ChunkPlan plan = chunk_plan(M, ROWBWD_MAXC, ROWBWD_ROWS);
   const bool want = (w0 || w1) && (dw0 || db0 || dw1 || db1);
-  if (want && (!ws || ws_bytes < (size_t)4 * nblk * D * sizeof(float))) return VGGT_ERR_SHAPE;
-  const int rpb = (M + nblk - 1) / nblk;
+  if (want && (!ws || ws_bytes < plan.bytes(4, D))) return VGGT_ERR_SHAPE;
   float* part = want ? (float*)ws : nullptr;
   hipStream_t s = (hipStream_t)stream;
-#define VGGT_HNRB(DD, MM, DT)                                                                                       \
-  headnorm_rope_bwd_kernel<DD, MM, DT><<<nblk, 256, 0, s>>>(pre, ldp, grad, ldg, M, H, hsplit, w0, w1, eps, pos,   \
-                                                            period, cos_tab, sin_tab, tab_len, rpb, part)
-#define VGGT_HNRB_M(DD, DT)                                                     \
-  switch (rope_mode) {                                                          \
-    case VGGT_ROPE_NONE: VGGT_HNRB(DD, VGGT_ROPE_NONE, DT); break;              \
-    case VGGT_ROPE_2D: VGGT_HNRB(DD, VGGT_ROPE_2D, DT); break;                  \
-    case VGGT_ROPE_1D: VGGT_HNRB(DD, VGGT_ROPE_1D, DT); break;                  \
-    default: return VGGT_ERR_UNSUPPORTED;                                       \
-  }
-  if (D == 64) {
-    if (dtype == VGGT_DTYPE_BF16) { VGGT_HNRB_M(64, VGGT_DTYPE_BF16) } else { VGGT_HNRB_M(64, VGGT_DTYPE_F32) }
-  } else {
-    if (dtype == VGGT_DTYPE_BF16) { VGGT_HNRB_M(128, VGGT_DTYPE_BF16) } else { VGGT_HNRB_M(128, VGGT_DTYPE_F32) }
-  }
-#undef VGGT_HNRB_M
-#undef VGGT_HNRB
-  if (part) {
-    float* outs[4] = {dw0, db0, dw1, db1};
-    // part layout [blk][a][D] -> finalize each (a) slice with stride 4*D per block
-    const float* parts[4] = {part, part + D, part + 2 * D, part + 3 * D};
-    const int strides[4] = {4 * D, 4 * D, 4 * D, 4 * D};
-    finalize_many(s, nblk, D, 1, 4, parts, strides, outs);
-  }
+  k<<<plan.nchunk, 256, 0, s>>>(pre, ldp, grad, ldg, M, H, hsplit, w0, w1, eps, pos, period, cos_tab, sin_tab, tab_len,
+                                (int)plan.rows, part);
+  // the kernel's layout is part[blk][dw0 | db0 | dw1 | db1][D]: four interleaved vectors, 4 * D floats a block
+  if (part)
+    finalize_many(s, plan.nchunk, D, 1,
+                  {{part, 4 * D, dw0}, {part + D, 4 * D, db0}, {part + 2 * D, 4 * D, dw1}, {part + 3 * D, 4 * D, db1}});
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -1113,17 +1104,15 @@ extern "C" int vggt_attention_small_bwd(const void* q, int64_t ldq, int64_t q_bs
                                         int64_t o_bstride, void* dq, int64_t lddq, int64_t dq_bstride, void* dk,
                                         void* dv, int64_t lddkv, int64_t dkv_bstride, int dtype, int batch, int heads,
                                         int nq, int nk, int D, float scale, void* stream) {
-  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || D <= 0) return VGGT_ERR_SHAPE;
-  if (dtype != VGGT_DTYPE_F32 && dtype != VGGT_DTYPE_BF16) return VGGT_ERR_UNSUPPORTED;
-  if (D % 2) return VGGT_ERR_SHAPE;
-  const int esz = dtype == VGGT_DTYPE_BF16 ? 2 : 4;
+  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || D <= 0 || D % 2) return VGGT_ERR_SHAPE;
   // two adjacent output columns per store: 4-B (bf16x2) / 4-B-aligned f32 pairs
-  if ((lddq | lddkv) % 2 || ((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % (2 * esz > 4 ? 4 : 2 * esz))
-    return VGGT_ERR_ALIGN;
+  if (int rc = check_mats({{q, dtype}, {k, dtype}, {v, dtype}, {dout, dtype}, {dq, dtype, lddq, 2, 4},
+                           {dk, dtype, lddkv, 2, 4}, {dv, dtype, lddkv, 2, 4}}))
+    return rc;
   const size_t lds = ((size_t)2 * nq * (D + 1) + (size_t)2 * nk * (D + 1) + (size_t)2 * nq * nk) * sizeof(float);
   if (lds > 64 * 1024) return VGGT_ERR_SHAPE;
   // 16-B operand reads when every row start of every operand is 16-B aligned
-  const int64_t al = 16 / esz;
+  const int64_t al = dtype == VGGT_DTYPE_BF16 ? 8 : 4;
   const int vec = D % 8 == 0 && (ldq | ldk | ldv | ldo) % al == 0 &&
                   ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout) % 16 == 0;
   attn_small_bwd_kernel<<<batch * heads, 256, lds, (hipStream_t)stream>>>(
@@ -1135,36 +1124,29 @@ extern "C" int vggt_attention_small_bwd(const void* q, int64_t ldq, int64_t q_bs
 
 extern "C" int vggt_wgrad_f32(const float* dy, int64_t ldy, const float* x, int64_t ldx, int M, int N, int K, float* dw,
                               int64_t ldw, int accumulate, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return VGGT_ERR_SHAPE;
-  if (N > 65535) return VGGT_ERR_SHAPE;
-  dim3 grid((K + 255) / 256, N);
-  wgrad_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dy, ldy, x, ldx, M, N, K, dw, ldw, accumulate, nullptr);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  return wgrad_f32(dy, ldy, x, ldx, M, N, K, dw, ldw, accumulate, nullptr, stream);
 }
 
 extern "C" int vggt_wgrad_bias_f32(const float* dy, int64_t ldy, const float* x, int64_t ldx, int M, int N, int K,
                                    float* dw, int64_t ldw, float* db, int accumulate, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !db) return VGGT_ERR_SHAPE;
-  if (N > 65535) return VGGT_ERR_SHAPE;
-  dim3 grid((K + 1 + 255) / 256, N);
-  wgrad_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dy, ldy, x, ldx, M, N, K, dw, ldw, accumulate, db);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  if (!db) return VGGT_ERR_SHAPE;
+  return wgrad_f32(dy, ldy, x, ldx, M, N, K, dw, ldw, accumulate, db, stream);
 }
 
-extern "C" size_t vggt_batch_dot_workspace_bytes(int B, int64_t n) { return (size_t)256 * (B > 0 ? B : 1) * sizeof(float); }
+// the cap's worth, whatever n
+extern "C" size_t vggt_batch_dot_workspace_bytes(int B, int64_t n) {
+  return ChunkPlan{BATCH_DOT_MAXC, 0}.bytes(1, B > 0 ? B : 1);
+}
 
 extern "C" int vggt_batch_dot_f32(const float* a, const float* c, int64_t bs, int B, int64_t n, float* out, void* ws,
                                   size_t ws_bytes, void* stream) {
   if (B <= 0 || n <= 0) return VGGT_ERR_SHAPE;
+  if (int rc = check_mats({{a}, {c}, {out}})) return rc;
   if (!ws || ws_bytes < vggt_batch_dot_workspace_bytes(B, n)) return VGGT_ERR_SHAPE;
-  int64_t nc = (n + 65535) / 65536;
-  if (nc > 256) nc = 256;
-  const int64_t per = (n + nc - 1) / nc;
+  const ChunkPlan plan = chunk_plan(n, BATCH_DOT_MAXC, BATCH_DOT_ELEMS);
   hipStream_t s = (hipStream_t)stream;
-  batch_dot_kernel<<<dim3((unsigned)nc, B), 256, 0, s>>>(a, c, bs, B, n, per, (float*)ws);
-  finalize_kernel<<<(B + 15) / 16, 256, 0, s>>>((const float*)ws, (int)nc, B, B, out, 0);
+  batch_dot_kernel<<<dim3(plan.nchunk, B), 256, 0, s>>>(a, c, bs, B, n, plan.rows, (float*)ws);
+  finalize_many(s, plan.nchunk, B, 0, {{(const float*)ws, B, out}});
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -1182,7 +1164,7 @@ extern "C" size_t vggt_wgrad_bf16_workspace_bytes(int M, int N, int K) {
 extern "C" int vggt_wgrad_bf16(const void* dy, int64_t ldy, const void* x, int64_t ldx, int M, int N, int K, float* dw,
                                int64_t ldw, int accumulate, void* ws, size_t ws_bytes, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 128) return VGGT_ERR_SHAPE;
-  if ((ldy | ldx) % 8 || ((uintptr_t)dy | (uintptr_t)x) % 16) return VGGT_ERR_ALIGN;
+  if (int rc = check_mats({{dy, VGGT_DTYPE_BF16, ldy, 8, 16}, {x, VGGT_DTYPE_BF16, ldx, 8, 16}, {dw}})) return rc;
   const size_t need = vggt_wgrad_bf16_workspace_bytes(M, N, K);
   if (!ws || ws_bytes < need) return VGGT_ERR_SHAPE;
   const int splits = (int)(need / ((size_t)N * K * sizeof(float)));

@@ -4,7 +4,7 @@
 of 64).  Each kernel is timed with HIP events over R back-to-back launches on
 the current stream.  Used to iterate on single kernels between full bench runs.
 
-    python scripts/kbench.py [--reps 20] [--only gemm,norm,attn]
+    python scripts/kbench.py [--reps 20] [--only gemm,norm,attn]   (train: not in the default set)
 """
 import argparse
 import json
@@ -115,6 +115,40 @@ def main():
         dw, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
         us = timeit(lambda: N.layernorm_bwd(xf, w, 1e-5, dy, dx, False, dw, db), args.reps)
         res["layernorm_bwd"] = {"us": round(us, 1), "gbs": round(M * C * 10 / us / 1e3, 1)}
+    if "train" in only:
+        # the backward kernels of train.hip at the alignment head's training shapes (layernorm_bwd: under "norm")
+        bf = lambda *s: torch.randn(*s, device=dev).bfloat16()  # noqa: E731
+        dy4, xk = bf(M, 4 * C), bf(M, C)
+        for Nn in (4 * C, 3 * C):
+            dw = torch.zeros(Nn, C, device=dev)
+            us = timeit(lambda: N.wgrad_bf16(dy4[:, :Nn], xk, dw, False), args.reps)
+            res[f"wgrad_bf16/{Nn}x{C}"] = {"us": round(us, 1), "tflops": round(2 * M * Nn * C / us / 1e6, 1)}
+        for Nn in (C, 4 * C):
+            out = torch.zeros(Nn, device=dev)
+            us = timeit(lambda: N.colsum(dy4[:, :Nn], out), args.reps)
+            res[f"colsum/{Nn}"] = {"us": round(us, 1), "gbs": round(M * Nn * 2 / us / 1e3, 1)}
+        dout, gam, dbr = torch.randn(M, C, device=dev), torch.rand(C, device=dev), torch.empty_like(xk)
+        dg, dbi = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        us = timeit(lambda: N.layerscale_bwd(dout, xk, gam, dbr, dg, dbi), args.reps)
+        res["layerscale_bwd/1024"] = {"us": round(us, 1), "gbs": round(M * C * 8 / us / 1e3, 1)}
+        pre4, dpre, db4 = bf(M, 4 * C), torch.empty_like(dy4), torch.zeros(4 * C, device=dev)
+        us = timeit(lambda: N.gelu_bwd(dy4, pre4, dpre, db4), args.reps)
+        res["gelu_bwd/4096"] = {"us": round(us, 1), "gbs": round(M * 4 * C * 6 / us / 1e3, 1)}
+        yy, xx = torch.meshgrid(torch.arange(37), torch.arange(37), indexing="ij")
+        pos = torch.cat([torch.zeros(5, 2, dtype=torch.long), torch.stack([yy.reshape(-1), xx.reshape(-1)], -1) + 1], 0)
+        rp = RopeTables(pos, D, 100.0, dev)
+        qpre, dq = bf(M, C), bf(M, C)
+        hw, hdw, hdb = torch.rand(D, device=dev), torch.zeros(D, device=dev), torch.zeros(D, device=dev)
+        us = timeit(lambda: N.headnorm_rope_bwd(qpre, dq, H, H, D, hw, None, 1e-5, rp.mode, rp.pos, rp.period, rp.cos,
+                                                rp.sin, hdw, hdb), args.reps)
+        res["headnorm_rope_bwd/16x64"] = {"us": round(us, 1), "gbs": round(M * C * 6 / us / 1e3, 1)}
+        # the temporal block as autograd.py calls it: one group per token position, the 16 frames attend each other
+        S, Ha = 16, 8
+        q, k, v, do = (bf(M, C) for _ in range(4))
+        gq, gkv = torch.empty_like(q), torch.empty(M, 2 * C, device=dev, dtype=torch.bfloat16)
+        us = timeit(lambda: N.attention_small_bwd(q, k, v, do, gq, gkv[:, :C], gkv[:, C:], M // S, Ha, S, S, C // Ha, S,
+                                                  S, S, S, S), args.reps)
+        res["attention_small_bwd/16x16"] = {"us": round(us, 1), "gbs": round(M * C * 14 / us / 1e3, 1)}
     if "attn" in only:
         qkv = (torch.randn(M, 3 * C, device=dev)).bfloat16()
         o = torch.empty(M, C, device=dev, dtype=torch.bfloat16)

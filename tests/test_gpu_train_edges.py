@@ -79,7 +79,11 @@ Tolerances (none is a measured constant; u = 2^-24, gamma_n = n u / (1 - n u)):
             with one rounding per stored value (worst 1.65 x, at D = 6, (1, 12)).
   poison    as above.
 Determinism: each reduction runs twice on the same inputs and the parameter gradients must be
-bitwise equal.  DESIGN.md (Training kernel edge tests) tabulates what was measured."""
+bitwise equal.
+Argument checks: `test_train_entry_error_returns` walks every entry's rules (dimensions, leading
+dimensions, pointer alignment, dtype codes, required pointers, workspace), one broken rule a call,
+against the codes the header documents; `test_dbias_is_colsum_of_the_stored_output` pins the one
+chunk plan and finalize behind the three column reductions.  DESIGN.md (Training kernel edge tests) tabulates what was measured."""
 import json
 import math
 import os
@@ -1209,6 +1213,221 @@ def test_batch_dot_f32_chunk_cap(N):
     assert got[0] == SENT and got[2] == SENT
     assert _bd_reach(n) == {"chunks": 256, "per_chunk": 65537}
     _done(errs, ("batch_dot_f32", n, _bd_reach(n)))
+
+
+# ================================================================== 9. the argument checks, rule by rule
+def _buf(rows, cols, dt=F32):
+    return torch.full((rows, cols), SENT, dtype=dt, device="cuda")
+
+
+def _rule_walk(L, entry, args, outs, rules):
+    """One valid call of the raw ctypes entry (VGGT_OK), then one call per rule with exactly that
+    argument changed; every call must return the documented code, and after a synchronise every
+    buffer of `outs` (refilled after the valid call) holds its sentinel bit for bit.  Returns the
+    number of calls."""
+    fn, base = getattr(L, entry), dict(args)
+    assert len(base) == len(args) == len(fn.argtypes), entry
+    rc = fn(*base.values())
+    assert rc == OK, f"{entry}: the valid call returned {rc}"
+    torch.cuda.synchronize()
+    for t in outs:
+        t.fill_(SENT)
+    calls = 1
+    for change, code in rules:
+        assert set(change) <= set(base), (entry, change)
+        rc = fn(*{**base, **change}.values())
+        assert rc == code, f"{entry} with {change}: returned {rc}, documented {code}"
+        calls += 1
+    torch.cuda.synchronize()
+    for i, t in enumerate(outs):
+        assert bool((_bits(t.cpu()) == _bits(torch.full_like(t, SENT).cpu())).all()), f"{entry}: buffer {i} was written"
+    return calls
+
+
+def _rules(shape=(), align=(), dtype=(), null=(), ok=()):
+    """(argument, broken value) pairs per documented code; `null` names required pointers."""
+    return ([({k: v}, ERR_SHAPE) for k, v in shape] + [({k: v}, ERR_ALIGN) for k, v in align] +
+            [({k: 7}, ERR_UNSUPPORTED) for k in dtype] + [({k: None}, ERR_SHAPE) for k in null] +
+            [({k: v}, OK) for k, v in ok])
+
+
+def test_train_entry_error_returns(N):
+    """Every entry point of train.hip at M = 4, N = 8 (or its smallest legal shape), through the raw
+    ctypes entries (`_native._dt` would refuse a bad dtype first): each dimension rule, each leading
+    dimension and pointer alignment rule, each dtype argument set to 7, each required pointer NULL, a
+    short and a NULL workspace -- and M == 0, which is VGGT_OK with nothing launched on the elementwise
+    and the row-backward entries and VGGT_ERR_SHAPE on the column reductions and the weight gradients.
+    Buffers are larger than any broken call could reach (a 16-column pitch, spare rows)."""
+    L = N.lib()
+    M, Nn, LD = 4, 8, 16
+    total = {}
+    ws = torch.empty(1 << 16, device="cuda")
+    wsr = [("ws", ws.data_ptr()), ("ws_bytes", ws.numel() * 4), ("stream", None)]
+    dims = [("M", 0), ("M", -1), ("N", 0), ("N", 6)]
+    ew_dims = [("M", -1), ("N", 0), ("N", 6)]
+
+    def short(nbytes):  # one float less than the entry needs; no workspace at all
+        return [("ws_bytes", nbytes - 4), ("ws", None)]
+
+    # ---- column reductions (one chunk at M = 4: a partial vector is N floats)
+    x, o = _buf(M + 2, LD), _buf(1, LD)
+    total["vggt_colsum"] = _rule_walk(
+        L, "vggt_colsum", [("x", x.data_ptr()), ("dtype", 0), ("ldx", LD), ("M", M), ("N", Nn), ("out", o.data_ptr()),
+                           ("accumulate", 0)] + wsr, [x, o],
+        _rules(shape=dims + short(Nn * 4), align=[("ldx", LD + 1), ("x", x.data_ptr() + 4)], dtype=["dtype"],
+               null=["x", "out"]))
+    assert int(L.vggt_colred_workspace_bytes(M, Nn)) == 2 * Nn * 4
+    d, b, g, ob, dg, db = _buf(M + 2, LD), _buf(M + 2, LD, BF), _buf(1, LD), _buf(M + 2, LD, BF), _buf(1, LD), _buf(1, LD)
+    total["vggt_layerscale_bwd"] = _rule_walk(
+        L, "vggt_layerscale_bwd",
+        [("dout", d.data_ptr()), ("ldd", LD), ("branch", b.data_ptr()), ("bdtype", 1), ("ldb", LD), ("gamma", g.data_ptr()),
+         ("dbranch", ob.data_ptr()), ("odtype", 1), ("ldo", LD), ("M", M), ("N", Nn), ("dgamma", dg.data_ptr()),
+         ("dbias", db.data_ptr())] + wsr, [ob, dg, db],
+        _rules(shape=dims + short(2 * Nn * 4),
+               align=[("ldd", LD + 1), ("ldb", LD + 1), ("ldo", LD + 1), ("dout", d.data_ptr() + 8),
+                      ("gamma", g.data_ptr() + 8), ("branch", b.data_ptr() + 4), ("dbranch", ob.data_ptr() + 4)],
+               dtype=["bdtype", "odtype"], null=["dout", "branch", "gamma", "dbranch"]))
+    h, p = _buf(M + 2, LD, BF), _buf(M + 2, LD)
+    total["vggt_gelu_bwd"] = _rule_walk(
+        L, "vggt_gelu_bwd",
+        [("dh", h.data_ptr()), ("dhdtype", 1), ("lddh", LD), ("pre", p.data_ptr()), ("predtype", 0), ("ldp", LD),
+         ("dpre", ob.data_ptr()), ("odtype", 1), ("ldo", LD), ("M", M), ("N", Nn), ("dbias", db.data_ptr())] + wsr,
+        [ob, db],
+        _rules(shape=dims + short(Nn * 4),
+               align=[("lddh", LD + 1), ("ldp", LD + 1), ("ldo", LD + 1), ("dh", h.data_ptr() + 4),
+                      ("pre", p.data_ptr() + 4), ("dpre", ob.data_ptr() + 4)],
+               dtype=["dhdtype", "predtype", "odtype"], null=["dh", "pre", "dpre"]))
+    # ---- elementwise
+    total["vggt_gelu_fwd"] = _rule_walk(
+        L, "vggt_gelu_fwd", [("x", p.data_ptr()), ("xdtype", 0), ("ldx", LD), ("y", ob.data_ptr()), ("ydtype", 1),
+                             ("ldy", LD), ("M", M), ("N", Nn), ("stream", None)], [ob],
+        _rules(shape=ew_dims, align=[("ldx", LD + 1), ("ldy", LD + 1), ("x", p.data_ptr() + 4), ("y", ob.data_ptr() + 4)],
+               dtype=["xdtype", "ydtype"], null=["x", "y"], ok=[("M", 0)]))
+    xo = _buf(M + 2, LD)
+    total["vggt_resid_scale_add_from"] = _rule_walk(
+        L, "vggt_resid_scale_add_from",
+        [("out", xo.data_ptr()), ("ldo", LD), ("x", x.data_ptr()), ("ldx", LD), ("branch", b.data_ptr()), ("bdtype", 1),
+         ("ldb", LD), ("gamma", g.data_ptr()), ("M", M), ("N", Nn), ("stream", None)], [xo],
+        _rules(shape=ew_dims,
+               align=[("ldo", LD + 1), ("ldx", LD + 1), ("ldb", LD + 1), ("out", xo.data_ptr() + 8),
+                      ("x", x.data_ptr() + 8), ("gamma", g.data_ptr() + 8), ("branch", b.data_ptr() + 4)],
+               dtype=["bdtype"], null=["out", "x", "branch", "gamma"], ok=[("M", 0)]))
+    total["vggt_resid_scale_add"] = _rule_walk(
+        L, "vggt_resid_scale_add",
+        [("x", xo.data_ptr()), ("ldx", LD), ("branch", b.data_ptr()), ("bdtype", 1), ("ldb", LD), ("gamma", g.data_ptr()),
+         ("M", M), ("N", Nn), ("stream", None)], [xo],
+        _rules(shape=ew_dims,
+               align=[("ldx", LD + 1), ("ldb", LD + 1), ("x", xo.data_ptr() + 8), ("gamma", g.data_ptr() + 8),
+                      ("branch", b.data_ptr() + 4)],
+               dtype=["bdtype"], null=["x", "branch", "gamma"], ok=[("M", 0)]))
+    # ---- transpose (no alignment or dtype rule: 2-byte elements one by one)
+    ts, td = _buf(M + 2, LD, BF), _buf(LD, LD, BF)
+    total["vggt_transpose_b16"] = _rule_walk(
+        L, "vggt_transpose_b16", [("src", ts.data_ptr()), ("lds", LD), ("rows", M), ("cols", Nn), ("dst", td.data_ptr()),
+                                  ("ldd", LD), ("rows_pad", M + 2), ("stream", None)], [td],
+        _rules(shape=[("rows", -1), ("cols", 0), ("rows_pad", M - 1)], null=["src", "dst"]))
+    # ---- LayerNorm backward (smallest C = 256; one block: a partial vector is C floats)
+    C = 256
+    lx, ly, ldx_, lw, lb = _buf(M + 2, C + 8), _buf(M + 2, C + 8, BF), _buf(M + 2, C + 8), _buf(1, C), _buf(1, C)
+    assert int(L.vggt_layernorm_bwd_workspace_bytes(M, C)) == 2 * C * 4
+    total["vggt_layernorm_bwd"] = _rule_walk(
+        L, "vggt_layernorm_bwd",
+        [("x", lx.data_ptr()), ("xdtype", 0), ("ldx", C + 8), ("w", None), ("eps", EPS), ("dy", ly.data_ptr()),
+         ("dydtype", 1), ("ldy", C + 8), ("dx", ldx_.data_ptr()), ("dxdtype", 0), ("lddx", C + 8), ("accumulate", 0),
+         ("M", M), ("C", C), ("group", M), ("xgs", 0), ("xoff", 0), ("ygs", 0), ("yoff", 0), ("dw", lw.data_ptr()),
+         ("db", lb.data_ptr())] + wsr, [ldx_, lw, lb],
+        _rules(shape=[("M", -1), ("C", 0), ("C", 768), ("C", 2048), ("group", 0)] + short(2 * C * 4),
+               align=[("ldx", C + 9), ("ldy", C + 9), ("lddx", C + 9), ("x", lx.data_ptr() + 4), ("dy", ly.data_ptr() + 4),
+                      ("dx", ldx_.data_ptr() + 4)],
+               dtype=["xdtype", "dydtype", "dxdtype"], null=["x", "dy", "dx"], ok=[("M", 0)]) +
+        [({"accumulate": 4}, ERR_UNSUPPORTED), ({"accumulate": 1, "dxdtype": 1}, ERR_UNSUPPORTED)])
+    # ---- per-head norm + RoPE backward (one head of 64, 2-D RoPE: every table is required)
+    D, tab = 64, 9
+    hp, hg = _buf(M + 2, D + 8, BF), _buf(M + 2, D + 8, BF)
+    hw = torch.ones(D, device="cuda")
+    pos = torch.zeros(M, 2, dtype=torch.int32, device="cuda")
+    cs, sn = (torch.zeros(tab, D // 2, device="cuda") for _ in range(2))
+    hd = [_buf(1, D) for _ in range(4)]
+    assert int(L.vggt_headnorm_rope_bwd_workspace_bytes(M, D)) == 4 * D * 4
+    total["vggt_headnorm_rope_bwd"] = _rule_walk(
+        L, "vggt_headnorm_rope_bwd",
+        [("pre", hp.data_ptr()), ("ldp", D + 8), ("grad", hg.data_ptr()), ("ldg", D + 8), ("dtype", 1), ("M", M), ("H", 1),
+         ("hsplit", 1), ("D", D), ("w0", hw.data_ptr()), ("w1", None), ("eps", EPS), ("rope_mode", ROPE_2D),
+         ("pos", pos.data_ptr()), ("period", M), ("cos", cs.data_ptr()), ("sin", sn.data_ptr()), ("tab_len", tab),
+         ("dw0", hd[0].data_ptr()), ("db0", hd[1].data_ptr()), ("dw1", hd[2].data_ptr()), ("db1", hd[3].data_ptr())] + wsr,
+        [hg] + hd,
+        _rules(shape=[("M", -1), ("H", 0), ("D", 32), ("hsplit", -1), ("hsplit", 2), ("period", 0), ("tab_len", 0)] +
+               short(4 * D * 4),
+               align=[("ldp", D + 4), ("ldg", D + 4), ("pre", hp.data_ptr() + 8), ("grad", hg.data_ptr() + 8)],
+               dtype=["dtype", "rope_mode"], null=["pre", "grad", "pos", "cos", "sin"], ok=[("M", 0)]))
+    # ---- small attention backward (bf16 pairs: 4-B output alignment, even output pitch)
+    Da = 8
+    aq, ak, av, ao = (_buf(M + 2, LD, BF) for _ in range(4))
+    gq, gk, gv = (_buf(M + 2, LD, BF) for _ in range(3))
+    total["vggt_attention_small_bwd"] = _rule_walk(
+        L, "vggt_attention_small_bwd",
+        [("q", aq.data_ptr()), ("ldq", LD), ("qbs", M), ("k", ak.data_ptr()), ("ldk", LD), ("kbs", M), ("v", av.data_ptr()),
+         ("ldv", LD), ("dout", ao.data_ptr()), ("ldo", LD), ("obs", M), ("dq", gq.data_ptr()), ("lddq", LD), ("dqbs", M),
+         ("dk", gk.data_ptr()), ("dv", gv.data_ptr()), ("lddkv", LD), ("dkvbs", M), ("dtype", 1), ("batch", 1),
+         ("heads", 1), ("nq", M), ("nk", M), ("D", Da), ("scale", 0.5), ("stream", None)], [gq, gk, gv],
+        _rules(shape=[("batch", 0), ("heads", 0), ("nq", 0), ("nk", 0), ("D", 0), ("D", 3)],
+               align=[("lddq", LD + 1), ("lddkv", LD + 1), ("dq", gq.data_ptr() + 2), ("dk", gk.data_ptr() + 2),
+                      ("dv", gv.data_ptr() + 2)],
+               dtype=["dtype"], null=["q", "k", "v", "dout", "dq", "dk", "dv"]))
+    # ---- weight gradients
+    wy, wx, ww, wb = _buf(M + 2, LD), _buf(M + 2, LD), _buf(Nn + 2, LD), _buf(1, LD)
+    wargs = [("dy", wy.data_ptr()), ("ldy", LD), ("x", wx.data_ptr()), ("ldx", LD), ("M", M), ("N", Nn), ("K", Nn),
+             ("dw", ww.data_ptr()), ("ldw", LD)]
+    wshape = [("M", 0), ("M", -1), ("N", 0), ("K", 0), ("N", 65536)]
+    total["vggt_wgrad_f32"] = _rule_walk(L, "vggt_wgrad_f32", wargs + [("accumulate", 0), ("stream", None)], [ww],
+                                         _rules(shape=wshape, null=["dy", "x", "dw"]))
+    total["vggt_wgrad_bias_f32"] = _rule_walk(
+        L, "vggt_wgrad_bias_f32", wargs + [("db", wb.data_ptr()), ("accumulate", 0), ("stream", None)], [ww, wb],
+        _rules(shape=wshape, null=["dy", "x", "dw", "db"]))
+    by, bx, bw = _buf(M + 2, 128 + 8, BF), _buf(M + 2, 128 + 8, BF), _buf(128, 128)
+    need = int(L.vggt_wgrad_bf16_workspace_bytes(M, 128, 128))
+    assert need == 128 * 128 * 4
+    total["vggt_wgrad_bf16"] = _rule_walk(
+        L, "vggt_wgrad_bf16", [("dy", by.data_ptr()), ("ldy", 136), ("x", bx.data_ptr()), ("ldx", 136), ("M", M),
+                               ("N", 128), ("K", 128), ("dw", bw.data_ptr()), ("ldw", 128), ("accumulate", 0)] + wsr, [bw],
+        _rules(shape=[("M", 0), ("M", -1), ("N", 0), ("K", 0), ("N", 192), ("K", 64)] + short(need),
+               align=[("ldy", 140), ("ldx", 140), ("dy", by.data_ptr() + 8), ("x", bx.data_ptr() + 8)],
+               null=["dy", "x", "dw"]))
+    # ---- batch dot
+    ba, bc, bo = _buf(2, 64), _buf(2, 64), _buf(1, 4)
+    need = int(L.vggt_batch_dot_workspace_bytes(2, 40))
+    total["vggt_batch_dot_f32"] = _rule_walk(
+        L, "vggt_batch_dot_f32", [("a", ba.data_ptr()), ("c", bc.data_ptr()), ("bs", 64), ("B", 2), ("n", 40),
+                                  ("out", bo.data_ptr())] + wsr, [bo],
+        _rules(shape=[("B", 0), ("n", 0)] + short(need), null=["a", "c", "out"]))
+    print("rule walk:", sum(total.values()), "calls;", total)
+
+
+# ================================================================== 10. one reducer behind every column sum
+@pytest.mark.parametrize("Nn", [4, 1028])
+@pytest.mark.parametrize("M", [1, 17, 273])
+def test_dbias_is_colsum_of_the_stored_output(N, M, Nn):
+    """dbias of vggt_gelu_bwd / vggt_layerscale_bwd into a zeroed buffer is, bit for bit, vggt_colsum of
+    the stored bf16 dpre / dbranch into a zeroed buffer: both add the same rounded values in the same
+    chunk and slice order (one chunk, a ragged second chunk, the 18-chunk finalize; N = 1028: a second
+    column block with one live thread).  The same with an fp32 output, where the stored value is the
+    unrounded product: the compiler would be free to contract it into the sum, and does not (the
+    property held on the library before the three entries shared their launcher, in both forms)."""
+    g = _gen(12, M, Nn)
+    errs = []
+    dh, pre = torch.randn(M, Nn, generator=g).to(BF).cuda(), (torch.randn(M, Nn, generator=g) * 2).to(BF).cuda()
+    dout, br = torch.randn(M, Nn, generator=g).cuda(), torch.randn(M, Nn, generator=g).to(BF).cuda()
+    gamma = (0.5 + torch.rand(Nn, generator=g)).cuda()
+    for nm, run in (("gelu_bwd", lambda o, s: N.gelu_bwd(dh, pre, o, s)),
+                    ("layerscale_bwd", lambda o, s: N.layerscale_bwd(dout, br, gamma, o, None, s))):
+        for odt in (BF, F32):
+            stored = torch.empty(M, Nn, dtype=odt, device="cuda")
+            dbias, cs = torch.zeros(Nn, device="cuda"), torch.zeros(Nn, device="cuda")
+            run(stored, dbias)
+            N.colsum(stored, cs, True)
+            _eq_bits(errs, f"{nm} M={M} N={Nn} out {_dtn(odt)}: dbias vs colsum of the stored output", dbias.cpu(),
+                     cs.cpu())
+    _done(errs, ("shared reducer", M, Nn, _reach_colred(M, Nn)))
 
 
 def test_zz_figures():
