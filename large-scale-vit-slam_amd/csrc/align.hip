@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "small_eig.h"
 
 namespace {
 
@@ -56,6 +57,8 @@ __device__ __forceinline__ float comb_at(const IrlsArgs& a, int b, int64_t i) {
 }
 
 // ---- radix select of the lower median of c, one 8-bit digit per pass
+// (not the shared select of points.hip / dense_pass.h: the key here is the raw bit pattern of c >= 0 formed
+// on the fly, the counters are 32-bit and thread 0 scans them serially, once per alignment)
 __global__ __launch_bounds__(NTH) void irls_hist(IrlsArgs a, int pass) {
   __shared__ uint32_t h[256];
   const int b = blockIdx.y;
@@ -113,12 +116,7 @@ __device__ __forceinline__ float weight_at(const IrlsArgs& a, const IrlsState& s
 }
 
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-  v = v + __shfl_xor(v, 32, 64);
-  v = v + __shfl_xor(v, 16, 64);
-  v = v + __shfl_xor(v, 8, 64);
-  v = v + __shfl_xor(v, 4, 64);
-  v = v + __shfl_xor(v, 2, 64);
-  v = v + __shfl_xor(v, 1, 64);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[w] = v;
@@ -206,44 +204,6 @@ __global__ __launch_bounds__(NTH) void irls_pass2(IrlsArgs a, int robust) {
   }
 }
 
-// ---- 3x3 symmetric eigen-decomposition (cyclic Jacobi, fp64)
-__device__ void jacobi3(double A[3][3], double V[3][3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    const double scale = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
-    if (off <= 1e-300 || off <= 1e-18 * scale) break;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        if (A[p][q] == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-        for (int k = 0; k < 3; ++k) {  // A = J^T A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-}
-
-__device__ __forceinline__ double det3(const double M[3][3]) {
-  return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-         M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-}
-
 // weighted Umeyama closed form from the reduced sums (pointAligned :159-219)
 __global__ void irls_solve(IrlsArgs a, int iter, int max_iters) {
   const int b = blockIdx.x;
@@ -272,72 +232,9 @@ __global__ void irls_solve(IrlsArgs a, int iter, int max_iters) {
     for (int j = 0; j < 3; ++j) Sg[i][j] = s2[3 * i + j] / W;
   const double varx = s2[9] / W;
   if (varx == 0.0) return no_solution();  // all weight on one source position: the reference's s is 0 / 0
-  // SVD Sg = U diag(sv) V^T via the eigen-decomposition of Sg^T Sg
-  double A[3][3], V[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) A[i][j] = Sg[0][i] * Sg[0][j] + Sg[1][i] * Sg[1][j] + Sg[2][i] * Sg[2][j];
-  jacobi3(A, V);
-  int ord[3] = {0, 1, 2};  // eigenvalues descending
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2 - i; ++j)
-      if (A[ord[j]][ord[j]] < A[ord[j + 1]][ord[j + 1]]) {
-        const int tmp = ord[j];
-        ord[j] = ord[j + 1];
-        ord[j + 1] = tmp;
-      }
-  double Vs[3][3], U[3][3], sv[3];
-  for (int k = 0; k < 3; ++k) {
-    for (int i = 0; i < 3; ++i) Vs[i][k] = V[i][ord[k]];
-  }
-  // u_k = Sg v_k / |Sg v_k| for the two largest; u_2 = u_0 x u_1, and v_2's
-  // sign chosen so that Sg v_2 = sv_2 u_2 with sv_2 >= 0 (a valid SVD pair)
-  for (int k = 0; k < 2; ++k) {
-    double u[3], nrm = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      u[i] = Sg[i][0] * Vs[0][k] + Sg[i][1] * Vs[1][k] + Sg[i][2] * Vs[2][k];
-      nrm += u[i] * u[i];
-    }
-    nrm = sqrt(nrm);
-    sv[k] = nrm;
-    for (int i = 0; i < 3; ++i) U[i][k] = nrm > 0 ? u[i] / nrm : (i == k ? 1.0 : 0.0);
-  }
-  // Rank <= 1 (collinear clouds, two points): Sg v_1 is rounding noise and its
-  // direction is not orthogonal to u_0.  Every entry of Sg is a sum of fp64
-  // products reduced through at most ceil(n / 65536) + 6 + 4 + 256 additions
-  // (thread, wave, block, the NB partials), so up to n = 2^24 it carries at most
-  // about 2^9 * 2^-53 = 2^-44 of sum w |y_c| |x_c| / W <= sqrt(var_x var_y), which is
-  // sv_0 for a rank-1 cloud; v_1's own error adds 2^-52 sv_0.  Below 2^-40 sv_0
-  // (16 x that bound) sv_1 carries no information about the rotation round
-  // u_0: take any unit vector orthogonal to u_0, from the axis u_0 is furthest from.
-  if (sv[1] <= 0x1p-40 * sv[0]) {
-    int j = 0;
-    for (int i = 1; i < 3; ++i)
-      if (fabs(U[i][0]) < fabs(U[j][0])) j = i;
-    double nrm = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      U[i][1] = (i == j ? 1.0 : 0.0) - U[j][0] * U[i][0];
-      nrm += U[i][1] * U[i][1];
-    }
-    nrm = sqrt(nrm);
-    for (int i = 0; i < 3; ++i) U[i][1] /= nrm;
-  }
-  U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-  U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-  U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  {
-    double u[3];
-    for (int i = 0; i < 3; ++i) u[i] = Sg[i][0] * Vs[0][2] + Sg[i][1] * Vs[1][2] + Sg[i][2] * Vs[2][2];
-    const double proj = u[0] * U[0][2] + u[1] * U[1][2] + u[2] * U[2][2];
-    if (proj < 0) {
-      for (int i = 0; i < 3; ++i) Vs[i][2] = -Vs[i][2];
-    }
-    sv[2] = fabs(proj);
-  }
-  // D = diag(1, 1, sign(det(U V^T)))
-  double UVt[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) UVt[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + U[i][2] * Vs[j][2];
-  const double dt = det3(UVt);
+  // R = U diag(1, 1, d) V^T with d = sign(det(U V^T)), 0 at a determinant of 0
+  double U[3][3], Vs[3][3], sv[3], dt;
+  svd3_for_umeyama(Sg, U, Vs, sv, &dt);
   const double d = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
   double R[3][3];
   for (int i = 0; i < 3; ++i)

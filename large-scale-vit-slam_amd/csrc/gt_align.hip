@@ -35,7 +35,7 @@
 // its own, as the reference's torch ops are.
 #include <math.h>
 
-#include "common.h"
+#include "dense_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -48,7 +48,6 @@ constexpr int GA_PASSES = 4;
 constexpr int GA_PER_THREAD = 16;   // pixels a lane takes before the grid stops growing
 constexpr int GA_MAX_BLOCKS = 1024;  // workgroups per element: one partial record each
 constexpr int64_t GA_MAX_N = 100000000;
-constexpr unsigned int GA_QNAN = 0x7fc00000u;
 
 // state_out: one record per element (VGGT_DEPTH_SCALE_STATE_BYTES)
 struct GaState {
@@ -76,6 +75,8 @@ struct GaWork {
 struct GaPartial {
   double sum;
   unsigned long long cnt;
+  __device__ GaPartial wave() const { return GaPartial{wave_sum(sum), wave_sum(cnt)}; }
+  __device__ void add(const GaPartial& o) { sum += o.sum, cnt += o.cnt; }
 };
 
 // ws: [B] GaWork | [B * GA_PASSES * GA_BINS] uint64 | [B * GA_MAX_BLOCKS] GaPartial
@@ -83,25 +84,10 @@ size_t ga_work_bytes(int B) { return ((size_t)B * sizeof(GaWork) + 15) / 16 * 16
 size_t ga_hist_bytes(int B) { return (size_t)B * GA_PASSES * GA_BINS * sizeof(unsigned long long); }
 size_t ga_partials_bytes(int B) { return (size_t)B * GA_MAX_BLOCKS * sizeof(GaPartial); }
 
-__device__ __forceinline__ bool ga_is_nan(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
-__device__ __forceinline__ bool ga_is_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // torch.max(a, b) / clamp_min: a NaN operand gives NaN
 __device__ __forceinline__ float ga_max(float a, float b) {
-  if (ga_is_nan(a) || ga_is_nan(b)) return __uint_as_float(GA_QNAN);
+  if (f32_is_nan(a) || f32_is_nan(b)) return __uint_as_float(F32_QNAN);
   return a < b ? b : a;
-}
-
-// vggt_kth_value_f32's key: -inf < finite < +inf < NaN, -0 == +0
-__device__ __forceinline__ unsigned int ga_key(float v) {
-  const unsigned int b = __float_as_uint(v);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-  if (b == 0x80000000u) return 0x80000000u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ga_unkey(unsigned int k) {
-  if (k == 0xffffffffu) return __uint_as_float(GA_QNAN);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 // One pixel (reference :281-295): the ratio and its weight, every operation rounded to fp32 on its own.
@@ -118,7 +104,7 @@ __device__ __forceinline__ GaTerm ga_term(float x, float conf, float y, bool m, 
   return t;
 }
 // A weight that is NaN, +-inf or negative counts as 0.
-__device__ __forceinline__ bool ga_weight_ok(float w_eff) { return ga_is_finite(w_eff) && !(w_eff < 0.f); }
+__device__ __forceinline__ bool ga_weight_ok(float w_eff) { return f32_is_finite(w_eff) && !(w_eff < 0.f); }
 
 // e with ldexp(wmax, e) in (2^35, 2^36]; 0 when wmax == 0
 __device__ __forceinline__ int ga_exponent(unsigned int wmax_bits) {
@@ -130,41 +116,6 @@ __device__ __forceinline__ int ga_exponent(unsigned int wmax_bits) {
 __device__ __forceinline__ unsigned long long ga_q(float w_eff, int e) {
   if (!ga_weight_ok(w_eff)) return 0ull;
   return (unsigned long long)rint(ldexp((double)w_eff, e));
-}
-
-// Four consecutive pixels from e of an element of n: one wide access when VEC and all four exist.
-template <bool VEC>
-__device__ __forceinline__ void ga_load4(const float* __restrict__ p, unsigned int e, unsigned int n, float (&v)[4]) {
-  if (VEC && e + 4 <= n) {
-    const float4 t = *reinterpret_cast<const float4*>(p + e);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = e + j < n ? p[e + j] : 0.f;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void ga_load4_mask(const uint8_t* __restrict__ p, unsigned int e, unsigned int n,
-                                              bool (&v)[4]) {
-  if (VEC && e + 4 <= n) {
-    const unsigned int t = *reinterpret_cast<const unsigned int*>(p + e);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = ((t >> (8 * j)) & 0xffu) != 0;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = e + j < n && p[e + j] != 0;
-  }
-}
-
-__device__ __forceinline__ double ga_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long ga_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 struct GaIn {
@@ -189,8 +140,8 @@ __global__ __launch_bounds__(GA_THREADS) void ga_sums_kernel(GaIn in, GaPartial*
   for (unsigned int e = 4u * (blockIdx.x * GA_THREADS + threadIdx.x); e < in.n; e += stride) {
     float y[4];
     bool m[4];
-    ga_load4<VEC>(gt, e, in.n, y);
-    ga_load4_mask<VEC>(mask, e, in.n, m);
+    load4<VEC>(gt, e, in.n, y);
+    load4_mask<VEC>(mask, e, in.n, m);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (e + j < in.n) {
@@ -199,16 +150,8 @@ __global__ __launch_bounds__(GA_THREADS) void ga_sums_kernel(GaIn in, GaPartial*
       }
     }
   }
-  sum = ga_wave_sum(sum), cnt = ga_wave_sum(cnt);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) s_part[tid >> 6] = GaPartial{sum, cnt};
-  __syncthreads();
-  if (tid == 0) {
-    GaPartial t = s_part[0];
-#pragma unroll
-    for (int k = 1; k < GA_WAVES; ++k) t.sum += s_part[k].sum, t.cnt += s_part[k].cnt;
-    partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-  }
+  const GaPartial t = block_reduce_record<GaPartial, GA_WAVES>(GaPartial{sum, cnt}, s_part);
+  if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 
 // One workgroup per element: the records in a fixed order, the mean, and the cleared selection state.
@@ -225,13 +168,8 @@ __global__ __launch_bounds__(GA_THREADS) void ga_mean_kernel(const GaPartial* __
     const GaPartial t = partials[(size_t)b * blocks + i];
     sum += t.sum, cnt += t.cnt;
   }
-  sum = ga_wave_sum(sum), cnt = ga_wave_sum(cnt);
-  if ((tid & 63) == 0) s_part[tid >> 6] = GaPartial{sum, cnt};
-  __syncthreads();
+  const GaPartial t = block_reduce_record<GaPartial, GA_WAVES>(GaPartial{sum, cnt}, s_part);
   if (tid != 0) return;
-  GaPartial t = s_part[0];
-#pragma unroll
-  for (int k = 1; k < GA_WAVES; ++k) t.sum += s_part[k].sum, t.cnt += s_part[k].cnt;
   const float mean = (float)(t.sum / (double)(t.cnt < 1 ? 1ull : t.cnt));
   GaWork w;
   w.below = 0, w.total = 0, w.wmax = 0, w.minkey = 0xffffffffu, w.prefix = 0;
@@ -254,15 +192,15 @@ __global__ __launch_bounds__(GA_THREADS) void ga_wmax_kernel(GaIn in, GaWork* __
   for (unsigned int e = 4u * (blockIdx.x * GA_THREADS + threadIdx.x); e < in.n; e += stride) {
     float x[4], c[4], y[4];
     bool m[4];
-    ga_load4<VEC>(pred, e, in.n, x);
-    ga_load4<VEC>(conf, e, in.n, c);
-    ga_load4<VEC>(gt, e, in.n, y);
-    ga_load4_mask<VEC>(mask, e, in.n, m);
+    load4<VEC>(pred, e, in.n, x);
+    load4<VEC>(conf, e, in.n, c);
+    load4<VEC>(gt, e, in.n, y);
+    load4_mask<VEC>(mask, e, in.n, m);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (e + j < in.n) {
         const GaTerm t = ga_term(x[j], c[j], y[j], m[j], min_depth);
-        minkey = min(minkey, ga_key(t.r));
+        minkey = min(minkey, f32_key_zeros_equal(t.r));
         // a non-negative finite float's bits order as the floats do; -0 counts as 0
         if (ga_weight_ok(t.w_eff) && t.w_eff > 0.f) wmax = max(wmax, __float_as_uint(t.w_eff));
       }
@@ -309,15 +247,15 @@ __global__ __launch_bounds__(GA_THREADS) void ga_hist_kernel(GaIn in, int pass, 
   for (unsigned int e = 4u * (blockIdx.x * GA_THREADS + tid); wk.wmax != 0 && e < in.n; e += stride) {
     float x[4], c[4], y[4];
     bool m[4];
-    ga_load4<VEC>(pred, e, in.n, x);
-    ga_load4<VEC>(conf, e, in.n, c);
-    ga_load4<VEC>(gt, e, in.n, y);
-    ga_load4_mask<VEC>(mask, e, in.n, m);
+    load4<VEC>(pred, e, in.n, x);
+    load4<VEC>(conf, e, in.n, c);
+    load4<VEC>(gt, e, in.n, y);
+    load4_mask<VEC>(mask, e, in.n, m);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (e + j < in.n && m[j]) {  // an unset pixel's weight is +-0 or NaN: q = 0
         const GaTerm t = ga_term(x[j], c[j], y[j], true, wk.min_depth);
-        const unsigned int key = ga_key(t.r);
+        const unsigned int key = f32_key_zeros_equal(t.r);
         if ((key & kmask) == prefix) {
           const unsigned long long q = ga_q(t.w_eff, e2);
           const unsigned int digit = (key >> shift) & (GA_BINS - 1);
@@ -348,12 +286,7 @@ __global__ __launch_bounds__(GA_BINS) void ga_pick_kernel(const unsigned long lo
   const unsigned long long own = hist_all[((size_t)b * GA_PASSES + pass) * GA_BINS + tid];
   cum[tid] = own;
   __syncthreads();
-  for (int o = 1; o < GA_BINS; o <<= 1) {  // inclusive scan
-    const unsigned long long add = tid >= o ? cum[tid - o] : 0ull;
-    __syncthreads();
-    cum[tid] += add;
-    __syncthreads();
-  }
+  scan256_inclusive(cum, tid);
   const GaWork wk = work[b];
   const unsigned long long total = pass == 0 ? cum[GA_BINS - 1] : wk.total;
   const unsigned long long upto = wk.below + cum[tid], below = upto - own;
@@ -377,7 +310,7 @@ __global__ __launch_bounds__(GA_BINS) void ga_pick_kernel(const unsigned long lo
     if (pass == 0) work[b].total = total;
   }
   if (mine && last) {
-    const float r = ga_unkey(key);
+    const float r = f32_unkey(key);
     scale_out[b] = r <= 0.f ? -r : r;  // reference :312; a NaN stays
     state[b].total = total;
     state[b].below = sel_below;
@@ -388,15 +321,10 @@ __global__ __launch_bounds__(GA_BINS) void ga_pick_kernel(const unsigned long lo
   }
 }
 
-int ga_blocks(int64_t n) {
-  const int64_t want = (n + (int64_t)GA_THREADS * GA_PER_THREAD - 1) / ((int64_t)GA_THREADS * GA_PER_THREAD);
-  return (int)(want < 1 ? 1 : (want > GA_MAX_BLOCKS ? GA_MAX_BLOCKS : want));
-}
-
 template <bool VEC>
 int ga_run(const GaIn& in, int B, float* scale_out, GaState* state, GaWork* work, unsigned long long* hist,
            GaPartial* partials, hipStream_t st) {
-  const int blocks = ga_blocks(in.n);
+  const int blocks = grid_for(in.n, GA_THREADS, GA_PER_THREAD, GA_MAX_BLOCKS);
   const dim3 grid((unsigned)blocks, (unsigned)B);
   ga_sums_kernel<VEC><<<grid, GA_THREADS, 0, st>>>(in, partials);
   HIP_LAUNCH_CHECK();

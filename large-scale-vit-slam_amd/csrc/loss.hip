@@ -24,7 +24,7 @@
 // Floating-point contraction is off for this file: which pixels pass `< thr'` must not depend on the compiler.
 #include <math.h>
 
-#include "common.h"
+#include "dense_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +38,6 @@ constexpr int DL_RED_MAX_BLOCKS = 1024;   // the sums: one partial record per wo
 constexpr int DL_AMAX_CHUNK = DL_THREADS * DL_PER_THREAD;  // pixels of a frame per amax workgroup (at least)
 constexpr int DL_AMAX_MAX_CHUNKS = 64;
 constexpr int64_t DL_MAX_TOTAL = 100000000;  // past it the reference subsamples at random (loss.py:441)
-constexpr unsigned int DL_QNAN = 0x7fc00000u;
 constexpr float DL_HARD_MAX = 100.f;
 constexpr float DL_EPS = 1e-8f;
 
@@ -57,6 +56,8 @@ static_assert(sizeof(DlState) == VGGT_DEPTH_LOSS_STATE_BYTES, "state layout");
 struct DlPartial {
   double sum_f, sum_c, sum_u;
   unsigned long long m;
+  __device__ DlPartial wave() const { return DlPartial{wave_sum(sum_f), wave_sum(sum_c), wave_sum(sum_u), wave_sum(m)}; }
+  __device__ void add(const DlPartial& o) { sum_f += o.sum_f, sum_c += o.sum_c, sum_u += o.sum_u, m += o.m; }
 };
 
 // ws: [B * S] amax keys | {rank int64, thr float} | DL_RED_MAX_BLOCKS partial records | the select's ws
@@ -64,26 +65,12 @@ size_t dl_keys_bytes(int64_t frames) { return ((size_t)frames * sizeof(unsigned 
 constexpr size_t DL_SCALARS_BYTES = 16;
 constexpr size_t DL_PARTIALS_BYTES = (size_t)DL_RED_MAX_BLOCKS * sizeof(DlPartial);
 
-__device__ __forceinline__ bool dl_is_nan(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
-__device__ __forceinline__ bool dl_is_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// torch's order (-inf < finite < +inf < NaN) as an unsigned key; every key is above 0, the cleared state
-__device__ __forceinline__ unsigned int dl_key(float v) {
-  const unsigned int b = __float_as_uint(v);
-  if (dl_is_nan(v)) return 0xffffffffu;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dl_unkey(unsigned int k) {
-  if (k == 0xffffffffu) return __uint_as_float(DL_QNAN);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // torch.clamp_min / clamp(max=): a NaN operand stays NaN
-__device__ __forceinline__ float dl_clamp_min(float x, float lo) { return dl_is_nan(x) ? x : (x < lo ? lo : x); }
-__device__ __forceinline__ float dl_clamp_max(float x, float hi) { return dl_is_nan(x) ? x : (x > hi ? hi : x); }
+__device__ __forceinline__ float dl_clamp_min(float x, float lo) { return f32_is_nan(x) ? x : (x < lo ? lo : x); }
+__device__ __forceinline__ float dl_clamp_max(float x, float hi) { return f32_is_nan(x) ? x : (x > hi ? hi : x); }
 // check_and_fix_inf_nan with hard_max = 100: non-finite -> 0, then clamp to +-100
 __device__ __forceinline__ double dl_scrub(float x) {
-  if (!dl_is_finite(x)) return 0.0;
+  if (!f32_is_finite(x)) return 0.0;
   return (double)(x > DL_HARD_MAX ? DL_HARD_MAX : (x < -DL_HARD_MAX ? -DL_HARD_MAX : x));
 }
 
@@ -94,48 +81,12 @@ struct DlTerm {
 };
 __device__ __forceinline__ DlTerm dl_term(float pred, float conf, float gt, float amax) {
   DlTerm t;
-  const float g = dl_is_finite(gt) ? gt : 0.f;  // check_and_fix_inf_nan(gt, hard_max=None)
+  const float g = f32_is_finite(gt) ? gt : 0.f;  // check_and_fix_inf_nan(gt, hard_max=None)
   t.p = dl_clamp_min(pred, DL_EPS);
   t.diff = logf(t.p) - logf(dl_clamp_min(g, DL_EPS));
   t.cn = conf / dl_clamp_min(amax, DL_EPS);
   t.val = fabsf(t.diff) * t.cn;
   return t;
-}
-
-// Four consecutive elements from e: one 128-bit (mask: 32-bit) access when VEC and all four exist, else one by one.
-template <bool VEC>
-__device__ __forceinline__ void dl_load4(const float* __restrict__ p, unsigned int e, unsigned int total,
-                                         float (&v)[4]) {
-  if (VEC && e + 4 <= total) {
-    const float4 t = *reinterpret_cast<const float4*>(p + e);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = e + j < total ? p[e + j] : 0.f;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void dl_load4_mask(const uint8_t* __restrict__ p, unsigned int e, unsigned int total,
-                                              bool (&v)[4]) {
-  if (VEC && e + 4 <= total) {
-    const unsigned int t = *reinterpret_cast<const unsigned int*>(p + e);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = ((t >> (8 * j)) & 0xffu) != 0;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = e + j < total && p[e + j] != 0;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void dl_store4(float* __restrict__ p, unsigned int e, unsigned int total,
-                                          const float (&v)[4]) {
-  if (VEC && e + 4 <= total) {
-    *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (e + j < total) p[e + j] = v[j];
-  }
 }
 
 // ----------------------------------------------------------------------------------------------- amax and n
@@ -156,17 +107,17 @@ __global__ __launch_bounds__(DL_THREADS) void dl_amax_kernel(const float* __rest
   // at most three pixels at either end with VEC (the first lanes of chunk 0), all of them without
   const unsigned int first = blockIdx.y * DL_THREADS + tid, step = gridDim.y * DL_THREADS;
   for (unsigned int e = begin + first; e < vb; e += step) {
-    key = max(key, dl_key(conf[e]));
+    key = max(key, f32_key(conf[e]));
     cnt += mask[e] ? 1u : 0u;
   }
   for (unsigned int e = ve + first; e < end; e += step) {
-    key = max(key, dl_key(conf[e]));
+    key = max(key, f32_key(conf[e]));
     cnt += mask[e] ? 1u : 0u;
   }
   for (unsigned int e = vb + 4u * (blockIdx.y * DL_THREADS + tid); e < ve; e += 4u * gridDim.y * DL_THREADS) {
     const float4 c = *reinterpret_cast<const float4*>(conf + e);
     const unsigned int m = *reinterpret_cast<const unsigned int*>(mask + e);
-    key = max(max(key, dl_key(c.x)), max(dl_key(c.y), max(dl_key(c.z), dl_key(c.w))));
+    key = max(max(key, f32_key(c.x)), max(f32_key(c.y), max(f32_key(c.z), f32_key(c.w))));
     cnt += ((m & 0xffu) ? 1u : 0u) + ((m & 0xff00u) ? 1u : 0u) + ((m & 0xff0000u) ? 1u : 0u) +
            ((m & 0xff000000u) ? 1u : 0u);
   }
@@ -212,21 +163,21 @@ __global__ __launch_bounds__(DL_THREADS) void dl_values_kernel(const float* __re
   for (unsigned int e = 4u * (blockIdx.x * DL_THREADS + threadIdx.x); e < total; e += stride) {
     float p[4], c[4], g[4], v[4];
     bool m[4];
-    dl_load4<VEC>(pred, e, total, p);
-    dl_load4<VEC>(conf, e, total, c);
-    dl_load4<VEC>(gt, e, total, g);
-    dl_load4_mask<VEC>(mask, e, total, m);
+    load4<VEC>(pred, e, total, p);
+    load4<VEC>(conf, e, total, c);
+    load4<VEC>(gt, e, total, g);
+    load4_mask<VEC>(mask, e, total, m);
     DlPos pos = dl_pos(e, hw);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (e + j < total) {
-        const float a = dl_unkey(keys[pos.f]);
+        const float a = f32_unkey(keys[pos.f]);
         if (pos.r == 0) amax[pos.f] = a;
-        v[j] = m[j] ? dl_term(p[j], c[j], g[j], a).val : __uint_as_float(DL_QNAN);
+        v[j] = m[j] ? dl_term(p[j], c[j], g[j], a).val : __uint_as_float(F32_QNAN);
         dl_next(pos, hw);
       }
     }
-    dl_store4<VEC>(val, e, total, v);
+    store4<VEC>(val, e, total, v);
   }
 }
 
@@ -240,12 +191,6 @@ __global__ void dl_rank_kernel(const long long* __restrict__ n_in, double q, lon
 }
 
 // ------------------------------------------------------------------------------------------------------ sums
-__device__ __forceinline__ double dl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(DL_THREADS) void dl_sums_kernel(const float* __restrict__ val, unsigned int total,
                                                              const float* __restrict__ thr_in,
@@ -257,10 +202,10 @@ __global__ __launch_bounds__(DL_THREADS) void dl_sums_kernel(const float* __rest
   const unsigned int stride = 4u * gridDim.x * DL_THREADS;
   for (unsigned int e = 4u * (blockIdx.x * DL_THREADS + threadIdx.x); e < total; e += stride) {
     float v[4];
-    dl_load4<VEC>(val, e, total, v);
+    load4<VEC>(val, e, total, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (e + j >= total) v[j] = __uint_as_float(DL_QNAN);  // as an unset pixel: no count, no sum
+      if (e + j >= total) v[j] = __uint_as_float(F32_QNAN);  // as an unset pixel: no count, no sum
       const float c = dl_clamp_max(v[j], DL_HARD_MAX);
       const double sc = dl_scrub(c);
       if (c < thr) ++m, sum_f += sc;
@@ -268,19 +213,8 @@ __global__ __launch_bounds__(DL_THREADS) void dl_sums_kernel(const float* __rest
       sum_u += dl_scrub(v[j]);
     }
   }
-  sum_f = dl_wave_sum(sum_f), sum_c = dl_wave_sum(sum_c), sum_u = dl_wave_sum(sum_u);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) s_part[tid >> 6] = DlPartial{sum_f, sum_c, sum_u, m};
-  __syncthreads();
-  if (tid == 0) {
-    DlPartial t = s_part[0];
-#pragma unroll
-    for (int k = 1; k < DL_WAVES; ++k)
-      t.sum_f += s_part[k].sum_f, t.sum_c += s_part[k].sum_c, t.sum_u += s_part[k].sum_u, t.m += s_part[k].m;
-    partials[blockIdx.x] = t;
-  }
+  const DlPartial t = block_reduce_record<DlPartial, DL_WAVES>(DlPartial{sum_f, sum_c, sum_u, m}, s_part);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 // One workgroup: the partial records in a fixed order, then the reference's branch.
@@ -297,20 +231,12 @@ __global__ __launch_bounds__(DL_THREADS) void dl_pick_kernel(const DlPartial* __
     const DlPartial t = partials[i];
     sum_f += t.sum_f, sum_c += t.sum_c, sum_u += t.sum_u, m += t.m;
   }
-  sum_f = dl_wave_sum(sum_f), sum_c = dl_wave_sum(sum_c), sum_u = dl_wave_sum(sum_u);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
-  if ((tid & 63) == 0) s_part[tid >> 6] = DlPartial{sum_f, sum_c, sum_u, m};
-  __syncthreads();
+  const DlPartial t = block_reduce_record<DlPartial, DL_WAVES>(DlPartial{sum_f, sum_c, sum_u, m}, s_part);
   if (tid != 0) return;
-  DlPartial t = s_part[0];
-#pragma unroll
-  for (int k = 1; k < DL_WAVES; ++k)
-    t.sum_f += s_part[k].sum_f, t.sum_c += s_part[k].sum_c, t.sum_u += s_part[k].sum_u, t.m += s_part[k].m;
   const long long n = *n_in, k = *rank;
   DlState s;
   s.n = n, s.k = k, s.m = k ? (long long)t.m : 0;
-  s.thr = k ? dl_clamp_max(*thr_in, DL_HARD_MAX) : __uint_as_float(DL_QNAN);
+  s.thr = k ? dl_clamp_max(*thr_in, DL_HARD_MAX) : __uint_as_float(F32_QNAN);
   s.pad = 0.f;
   double sum = 0.0;
   if (n < 100) {
@@ -344,10 +270,10 @@ __global__ __launch_bounds__(DL_THREADS) void dl_bwd_kernel(const float* __restr
     if (kind != VGGT_DEPTH_LOSS_SKIPPED) {  // uniform
       float p[4], c[4], g[4];
       bool m[4];
-      dl_load4<VEC>(pred, e, total, p);
-      dl_load4<VEC>(conf, e, total, c);
-      dl_load4<VEC>(gt, e, total, g);
-      dl_load4_mask<VEC>(mask, e, total, m);
+      load4<VEC>(pred, e, total, p);
+      load4<VEC>(conf, e, total, c);
+      load4<VEC>(gt, e, total, g);
+      load4_mask<VEC>(mask, e, total, m);
       DlPos pos = dl_pos(e, hw);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -355,7 +281,7 @@ __global__ __launch_bounds__(DL_THREADS) void dl_bwd_kernel(const float* __restr
           if (m[j]) {
             const DlTerm t = dl_term(p[j], c[j], g[j], amax[pos.f]);
             // the scrub and every clamp pass gradient on [-100, 100] only; the filter keeps val < thr'
-            bool on = dl_is_finite(t.val) && t.val <= DL_HARD_MAX && t.val >= -DL_HARD_MAX && p[j] >= DL_EPS;
+            bool on = f32_is_finite(t.val) && t.val <= DL_HARD_MAX && t.val >= -DL_HARD_MAX && p[j] >= DL_EPS;
             if (kind == VGGT_DEPTH_LOSS_FILTERED) on = on && t.val < thr;
             const float sign = t.diff > 0.f ? 1.f : (t.diff < 0.f ? -1.f : 0.f);
             if (on) d[j] = up * sign * t.cn / t.p / denom;
@@ -364,16 +290,12 @@ __global__ __launch_bounds__(DL_THREADS) void dl_bwd_kernel(const float* __restr
         }
       }
     }
-    dl_store4<VEC>(dpred, e, total, d);
+    store4<VEC>(dpred, e, total, d);
   }
 }
 
 bool dl_dims_ok(int B, int S, int H, int W) { return B >= 1 && S >= 1 && H >= 1 && W >= 1; }
 int64_t dl_total(int B, int S, int H, int W) { return (int64_t)B * S * H * W; }
-int dl_blocks(int64_t total, int cap) {
-  const int64_t want = (total + (int64_t)DL_THREADS * DL_PER_THREAD - 1) / ((int64_t)DL_THREADS * DL_PER_THREAD);
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
 bool dl_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 }  // namespace
@@ -405,7 +327,7 @@ extern "C" int vggt_depth_loss_values(const float* pred, const float* conf, cons
   int chunks = (int)((hw + DL_AMAX_CHUNK - 1) / DL_AMAX_CHUNK);
   chunks = chunks > DL_AMAX_MAX_CHUNKS ? DL_AMAX_MAX_CHUNKS : chunks;
   const dim3 agrid((unsigned)frames, (unsigned)chunks);
-  const int blocks = dl_blocks(total, DL_MAX_BLOCKS);
+  const int blocks = grid_for(total, DL_THREADS, DL_PER_THREAD, DL_MAX_BLOCKS);
   const uint8_t* mk = (const uint8_t*)mask;
   if (vec) {
     dl_amax_kernel<true><<<agrid, DL_THREADS, 0, st>>>(conf, mk, hw, keys, (unsigned long long*)n_out);
@@ -440,7 +362,7 @@ extern "C" int vggt_depth_loss_reduce(const float* val, const int64_t* n, int B,
   const int rc = vggt_kth_value_f32_devrank(val, total, (const int64_t*)rank, thr, kth_ws,
                                             vggt_kth_value_ws_bytes(total), stream);
   if (rc != VGGT_OK) return rc;
-  const int blocks = dl_blocks(total, DL_RED_MAX_BLOCKS);
+  const int blocks = grid_for(total, DL_THREADS, DL_PER_THREAD, DL_RED_MAX_BLOCKS);
   if (dl_aligned16(val))
     dl_sums_kernel<true><<<blocks, DL_THREADS, 0, st>>>(val, (unsigned int)total, thr, partials);
   else
@@ -465,7 +387,7 @@ extern "C" int vggt_depth_loss_bwd(const float* pred, const float* conf, const f
   const unsigned int hw = (unsigned int)((int64_t)H * W);
   const bool vec = dl_aligned16(pred) && dl_aligned16(conf) && dl_aligned16(gt) && dl_aligned16(dpred) &&
                    (uintptr_t)mask % 4 == 0;
-  const int blocks = dl_blocks(total, DL_MAX_BLOCKS);
+  const int blocks = grid_for(total, DL_THREADS, DL_PER_THREAD, DL_MAX_BLOCKS);
   const uint8_t* mk = (const uint8_t*)mask;
   if (vec)
     dl_bwd_kernel<true><<<blocks, DL_THREADS, 0, st>>>(pred, conf, gt, mk, amax, (const DlState*)state, grad_loss, hw,

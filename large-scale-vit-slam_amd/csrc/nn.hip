@@ -215,12 +215,6 @@ __global__ __launch_bounds__(256) void nn1_unpack_kernel(const unsigned long lon
   }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Stage 1: workgroup blockIdx.x sums rows blockIdx.x * 256 + tid + k * gridDim.x * 256 (fixed for a given n_max).
 __global__ __launch_bounds__(PS_THREADS) void pair_stats_partial_kernel(
     const float* __restrict__ x, int64_t x_bs, const int64_t* __restrict__ x_len, int64_t n_max,
@@ -252,7 +246,7 @@ __global__ __launch_bounds__(PS_THREADS) void pair_stats_partial_kernel(
   }
 #pragma unroll
   for (int k = 0; k < PS_VALS; ++k) {
-    const double v = wave_sum_f64(a[k]);
+    const double v = wave_sum(a[k]);
     if ((tid & 63) == 0) red[tid >> 6][k] = v;
   }
   __syncthreads();

@@ -21,12 +21,6 @@ __device__ __forceinline__ void unpack_bf4(uint2 u, float (&f)[4]) {
 // per lane and rsqrtf left a row up to 5 x as far from fp64 as a plain fp32 evaluation
 // (C = 4096, mean 1000: 3.3e-7 against 6.4e-8 of the row norm), which only a bf16
 // rounding hides.  bf16 outputs keep the fp32 statistics (and their bits).
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int NV, bool IN_BF16, bool OUT_BF16>
 __global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t ldx, const float* __restrict__ w,
                                                         const float* __restrict__ b, float eps, int M, void* y,
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t l
     for (int i = 0; i < NV; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) sd += (double)v[i][j];
-    const double mean = wave_sum_f64(sd) / C;  // a quotient: the mean of a constant row is exact for every C
+    const double mean = wave_sum(sd) / C;  // a quotient: the mean of a constant row is exact for every C
     double qd = 0.;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* x, int64_t l
         const double d = (double)v[i][j] - mean;
         qd = fma(d, d, qd);
       }
-    const double rstd = 1.0 / sqrt(wave_sum_f64(qd) / C + (double)eps);
+    const double rstd = 1.0 / sqrt(wave_sum(qd) / C + (double)eps);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = i * 256 + lane * 4;

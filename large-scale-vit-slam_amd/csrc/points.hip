@@ -34,7 +34,7 @@
 // below, SPEC_ASSUMPTIONS.md).  (HIP's __fmul_rn / __fadd_rn are plain operators and contract like them.)
 #include <math.h>
 
-#include "common.h"
+#include "dense_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -57,22 +57,9 @@ struct KthState {
 constexpr size_t KTH_HIST_BYTES = (size_t)KTH_PASSES * KTH_BINS * sizeof(unsigned long long);
 constexpr size_t KTH_WS_BYTES = KTH_HIST_BYTES + sizeof(KthState);
 
-// torch's order: -inf < finite < +inf < NaN, -0 == +0.  Negative floats flip all bits, others set the sign bit;
-// -0 takes +0's key and every NaN the largest key.
-__device__ __forceinline__ unsigned int kth_key(float v) {
-  const unsigned int b = __float_as_uint(v);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-  if (b == 0x80000000u) return 0x80000000u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float kth_unkey(unsigned int k) {
-  if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __device__ __forceinline__ void kth_add(unsigned int* hist, float v, unsigned int prefix, unsigned int mask,
                                         int shift, bool in_range) {
-  const unsigned int key = kth_key(v);
+  const unsigned int key = f32_key_zeros_equal(v);  // torch.kthvalue's order: -0 == +0
   const bool take = in_range && (key & mask) == prefix;
   const unsigned int digit = (key >> shift) & (KTH_BINS - 1);
   const unsigned long long takers = __ballot(take);
@@ -121,12 +108,7 @@ __global__ __launch_bounds__(KTH_BINS) void kth_pick_kernel(const unsigned long 
   const unsigned long long own = hist_all[(size_t)pass * KTH_BINS + tid];
   cum[tid] = own;
   __syncthreads();
-  for (int o = 1; o < KTH_BINS; o <<= 1) {  // inclusive scan
-    const unsigned long long add = tid >= o ? cum[tid - o] : 0ull;
-    __syncthreads();
-    cum[tid] += add;
-    __syncthreads();
-  }
+  scan256_inclusive(cum, tid);
   const unsigned long long rank = state->rank;
   const unsigned long long upto = cum[tid], below = upto - own;
   __syncthreads();  // every lane has read the rank before one rewrites it
@@ -135,7 +117,7 @@ __global__ __launch_bounds__(KTH_BINS) void kth_pick_kernel(const unsigned long 
     const unsigned int prefix = state->prefix | ((unsigned int)tid << shift);
     state->prefix = prefix;
     state->rank = rank - below;
-    if (pass == KTH_PASSES - 1) *out = kth_unkey(prefix);
+    if (pass == KTH_PASSES - 1) *out = f32_unkey(prefix);
   }
 }
 
@@ -157,8 +139,7 @@ __global__ void kth_init_devrank_kernel(KthState* __restrict__ state, const long
 
 // The four histogram / pick rounds, after the state is initialised.
 int kth_passes(const float* x, int64_t n, float* out, unsigned long long* hist, KthState* state, hipStream_t st) {
-  const int64_t want = (n + (int64_t)KTH_THREADS * KTH_PER_THREAD - 1) / ((int64_t)KTH_THREADS * KTH_PER_THREAD);
-  const int blocks = (int)(want < 1 ? 1 : (want > KTH_MAX_BLOCKS ? KTH_MAX_BLOCKS : want));
+  const int blocks = grid_for(n, KTH_THREADS, KTH_PER_THREAD, KTH_MAX_BLOCKS);
   for (int pass = 0; pass < KTH_PASSES; ++pass) {
     kth_hist_kernel<<<blocks, KTH_THREADS, 0, st>>>(x, n, pass, hist, state);
     HIP_LAUNCH_CHECK();
@@ -231,8 +212,7 @@ __global__ __launch_bounds__(MC_THREADS) void mask_count_kernel(const uint8_t* _
       mine += sub_mask(mask, row / Ho, H, W, bl_axis(ho, H, sh), bl_axis(wo, W, sw)) ? 1u : 0u;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  mine = wave_sum(mine);
   if ((tid & 63) == 0) part[tid >> 6] = mine;
   __syncthreads();
   if (tid == 0) {

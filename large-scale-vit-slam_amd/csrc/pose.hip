@@ -12,6 +12,7 @@
 // sign is arbitrary in both, SURVEY Appendix A.7 -- and irrelevant here: the
 // mean only enters through quat_to_mat, which is even in q).
 #include "common.h"
+#include "small_eig.h"
 
 namespace {
 
@@ -91,51 +92,6 @@ __device__ Aff inv_se3(const Aff& a) {
     for (int j = 0; j < 3; ++j) o.r[i][j] = a.r[j][i];
   for (int i = 0; i < 3; ++i) o.t[i] = -(o.r[i][0] * a.t[0] + o.r[i][1] * a.t[1] + o.r[i][2] * a.t[2]);
   return o;
-}
-
-// Largest-eigenvalue unit eigenvector of a symmetric 4x4 (cyclic Jacobi, fp64).
-__device__ void top_eigvec4(const double Min[4][4], double* v) {
-  double A[4][4], V[4][4];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      A[i][j] = Min[i][j];
-      V[i][j] = i == j ? 1.0 : 0.0;
-    }
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 4; ++p)
-      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
-    if (off < 1e-60) break;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
-        if (fabs(A[p][q]) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {  // A <- J^T A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int b = 0;
-  for (int i = 1; i < 4; ++i)
-    if (A[i][i] > A[b][b]) b = i;
-  double n = 0.0;
-  for (int k = 0; k < 4; ++k) n += V[k][b] * V[k][b];
-  n = sqrt(n);
-  for (int k = 0; k < 4; ++k) v[k] = V[k][b] / n;
 }
 
 constexpr int MAX_OV = 64;
@@ -261,56 +217,6 @@ __global__ __launch_bounds__(64) void pose_compose_kernel(
       po[12] = 0.f; po[13] = 0.f; po[14] = 0.f; po[15] = 1.f;
     }
   }
-}
-
-// top_eigvec4 with the winning column picked by selects: its V[k][b] with a run-time b
-// puts V into scratch (144 B per lane in pose_compose_kernel, whose code stays as it is).
-// The sweeps are top_eigvec4's, operation for operation: keep the two bodies in step.
-__device__ void top_eigvec4_sel(const double Min[4][4], double* v) {
-  double A[4][4], V[4][4];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      A[i][j] = Min[i][j];
-      V[i][j] = i == j ? 1.0 : 0.0;
-    }
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 4; ++p)
-      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
-    if (off < 1e-60) break;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
-        if (fabs(A[p][q]) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {  // A <- J^T A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int b = 0;
-  double best = A[0][0];
-  for (int i = 1; i < 4; ++i)
-    if (A[i][i] > best) { best = A[i][i]; b = i; }
-  double col[4];
-  for (int k = 0; k < 4; ++k) col[k] = b == 0 ? V[k][0] : b == 1 ? V[k][1] : b == 2 ? V[k][2] : V[k][3];
-  double n = 0.0;
-  for (int k = 0; k < 4; ++k) n += col[k] * col[k];
-  n = sqrt(n);
-  for (int k = 0; k < 4; ++k) v[k] = col[k] / n;
 }
 
 // Per-chunk pose algebra of the pose-aligned VGGT (poseAligned_wrapped_vggt.py:74-130,
@@ -450,7 +356,7 @@ __global__ __launch_bounds__(64) void pose_align_kernel(
       double Md[4][4], v[4];
       for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) Md[i][j] = M[i][j];
-      top_eigvec4_sel(Md, v);
+      top_eigvec4(Md, v);
       float e[7] = {t[0] / (float)ov, t[1] / (float)ov, t[2] / (float)ov, (float)v[0], (float)v[1], (float)v[2],
                     (float)v[3]};
       s_mean = enc_to_aff(e);  // pose_encoding_to_extri(mean), :122
@@ -496,105 +402,13 @@ __global__ __launch_bounds__(64) void pose_align_kernel(
 
 // ---- GT alignment of a merged sequence from its poses (alignment.py:131-242, :325-370, :6-59)
 
-// 3x3 symmetric eigen-decomposition (cyclic Jacobi, fp64) and determinant: copies of align.hip's
-// jacobi3 / det3, operation for operation (keep the bodies in step).
-__device__ void jacobi3(double A[3][3], double V[3][3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    const double scale = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
-    if (off <= 1e-300 || off <= 1e-18 * scale) break;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        if (A[p][q] == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-        for (int k = 0; k < 3; ++k) {  // A = J^T A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-}
-
-__device__ __forceinline__ double det3(const double M[3][3]) {
-  return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-         M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-}
-
 // Umeyama's closed form (alignment.py:6-59) from the centred cross-covariance Sg = E[(y - my)(x - mx)^T]
-// and sigma_x = E|x - mx|^2: R = U diag(1, 1, d) V^T, c = tr(D diag(1, 1, d)) / sigma_x.  The SVD as
-// irls_solve (align.hip) takes it: V from Jacobi on Sg^T Sg, u_k = Sg v_k / |Sg v_k|, u_2 = u_0 x u_1
-// and v_2's sign so that sv_2 >= 0; det(U) is then +1 and d = sign(det(U V^T)) is the reference's
-// det(u) det(v) < 0 test for any valid SVD pair (d v_2 does not depend on v_2's sign).
+// and sigma_x = E|x - mx|^2: R = U diag(1, 1, d) V^T, c = tr(D diag(1, 1, d)) / sigma_x, on the SVD that
+// irls_solve (align.hip) takes too (small_eig.h).
 __device__ void umeyama3(const double Sg[3][3], double sigma_x, double R[3][3], double* c_out) {
-  double A[3][3], V[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) A[i][j] = Sg[0][i] * Sg[0][j] + Sg[1][i] * Sg[1][j] + Sg[2][i] * Sg[2][j];
-  jacobi3(A, V);
-  int ord[3] = {0, 1, 2};  // eigenvalues descending
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2 - i; ++j)
-      if (A[ord[j]][ord[j]] < A[ord[j + 1]][ord[j + 1]]) {
-        const int tmp = ord[j];
-        ord[j] = ord[j + 1];
-        ord[j + 1] = tmp;
-      }
-  double Vs[3][3], U[3][3], sv[3];
-  for (int k = 0; k < 3; ++k)
-    for (int i = 0; i < 3; ++i) Vs[i][k] = V[i][ord[k]];
-  for (int k = 0; k < 2; ++k) {
-    double u[3], nrm = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      u[i] = Sg[i][0] * Vs[0][k] + Sg[i][1] * Vs[1][k] + Sg[i][2] * Vs[2][k];
-      nrm += u[i] * u[i];
-    }
-    nrm = sqrt(nrm);
-    sv[k] = nrm;
-    for (int i = 0; i < 3; ++i) U[i][k] = nrm > 0 ? u[i] / nrm : (i == k ? 1.0 : 0.0);
-  }
-  // rank <= 1 (collinear centres): Sg v_1 is rounding noise, take any unit vector orthogonal to u_0
-  // (irls_solve derives the 2^-40 threshold); the rotation round u_0 is then not determined by the data
-  if (sv[1] <= 0x1p-40 * sv[0]) {
-    int j = 0;
-    for (int i = 1; i < 3; ++i)
-      if (fabs(U[i][0]) < fabs(U[j][0])) j = i;
-    double nrm = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      U[i][1] = (i == j ? 1.0 : 0.0) - U[j][0] * U[i][0];
-      nrm += U[i][1] * U[i][1];
-    }
-    nrm = sqrt(nrm);
-    for (int i = 0; i < 3; ++i) U[i][1] /= nrm;
-  }
-  U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-  U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-  U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  {
-    double u[3];
-    for (int i = 0; i < 3; ++i) u[i] = Sg[i][0] * Vs[0][2] + Sg[i][1] * Vs[1][2] + Sg[i][2] * Vs[2][2];
-    const double proj = u[0] * U[0][2] + u[1] * U[1][2] + u[2] * U[2][2];
-    if (proj < 0)
-      for (int i = 0; i < 3; ++i) Vs[i][2] = -Vs[i][2];
-    sv[2] = fabs(proj);
-  }
-  double UVt[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) UVt[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + U[i][2] * Vs[j][2];
-  const double d = det3(UVt) < 0 ? -1.0 : 1.0;  // the reflection fix (:39-40)
+  double U[3][3], Vs[3][3], sv[3], det;
+  svd3_for_umeyama(Sg, U, Vs, sv, &det);
+  const double d = det < 0 ? -1.0 : 1.0;  // the reflection fix (:39-40)
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + d * U[i][2] * Vs[j][2];
   *c_out = (sv[0] + sv[1] + d * sv[2]) / sigma_x;  // sigma_x == 0: inf or NaN, as the reference's 1 / sigma_x

@@ -399,12 +399,6 @@ __global__ __launch_bounds__(256) void linear_f32_reduce(const float* __restrict
   }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------------
 // Small-window attention: one wave per (group, head); K/V of the group in
 // LDS as f32; keys spread over lanes (<= 2 per lane, nk <= 128), each query
@@ -666,13 +660,13 @@ __global__ __launch_bounds__(64) void headnorm_rope_f32_kernel(float* __restrict
   }
   __syncthreads();
   if (w) {
-    const double mean = wave_sum_f64(s) / D;
+    const double mean = wave_sum(s) / D;
     double qv = 0.;
     for (int d = lane; d < D; d += 64) {
       const double t = (double)xs[d] - mean;
       qv = fma(t, t, qv);
     }
-    const double rstd = 1.0 / sqrt(wave_sum_f64(qv) / D + (double)eps);
+    const double rstd = 1.0 / sqrt(wave_sum(qv) / D + (double)eps);
     __syncthreads();
     for (int d = lane; d < D; d += 64)
       xs[d] = (float)(((double)xs[d] - mean) * rstd * (double)w[d] + (b ? (double)b[d] : 0.));

@@ -15,9 +15,12 @@ whole calls (the host work between the launches included); ``--rounds`` rounds a
 every round is listed and the median reported.  A call with GT scales the depth in place: the GT translations are
 the predicted ones plus 0.1 % noise, so the scale stays near 1 and the depth does not drift away.  ``--forward``
 adds the whole per-chunk forward (aggregator, camera and depth heads, alignment) of a synthetic-weight model, hip
-against torch.  Prints one JSON line per measurement.
+against torch.  ``--compose`` times vggt_pose_compose (the feature-aligned model's composition, one launch) alone
+instead, through the C ABI into preallocated outputs, with a context (the Markley mean over the overlap) and without.
+Prints one JSON line per measurement.
 
     python scripts/bench_pose_aligned.py [--frames 75] [--overlap 30] [--rounds 3] [--seconds 1.5] [--forward]
+    python scripts/bench_pose_aligned.py --compose
 """
 import argparse
 import json
@@ -101,6 +104,35 @@ def report(what, ms, against="hip"):
     print(json.dumps(rec), flush=True)
 
 
+def compose_only(enc, prev, B, S, ov, dev, rounds, win):
+    """vggt_pose_compose alone: device events around the one call, every round listed."""
+    from aligned_vggt import _native as N
+    g = torch.Generator().manual_seed(1)
+    q = torch.randn(B, S, 4, generator=g)
+    frame = torch.cat([0.1 * torch.randn(B, S, 3, generator=g), q / q.norm(dim=-1, keepdim=True)], -1)
+    chunk = torch.cat([frame[:, 0], 1.0 + 0.1 * torch.rand(B, 1, generator=g)], -1).to(dev).contiguous()
+    frame = frame[:, 1:].to(dev).contiguous()
+    cam = enc["pose_enc"].contiguous()
+    out, pt = torch.empty(B, S, 9, device=dev), torch.empty(B, 4, 4, device=dev)
+    L, p = N.lib(), N._p
+
+    def call(ctx):
+        def run():
+            rc = L.vggt_pose_compose(p(chunk), p(frame), p(cam), p(ctx), ctx.shape[1] if ctx is not None else 0, None,
+                                     B, S, ov, H, W, p(out), p(pt), N._stream())
+            assert rc == 0, rc
+        return run
+
+    for name, ctx in (("context", prev), ("no context", None)):
+        call(ctx)()
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all())
+        ms = rounds_of({"hip": call(ctx)}, rounds, win)
+        print(json.dumps({"what": f"vggt_pose_compose B={B} S={S} ov={ov} {name}",
+                          "hip_us_rounds": [round(1e3 * t, 2) for t in ms["hip"]],
+                          "hip_us": round(1e3 * median(ms["hip"]), 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=75)
@@ -108,12 +140,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=1.5, help="timed work per side, over all rounds")
     ap.add_argument("--forward", action="store_true", help="also time the whole per-chunk forward")
+    ap.add_argument("--compose", action="store_true", help="time vggt_pose_compose alone, and nothing else")
     args = ap.parse_args()
     from aligned_vggt.models import poseAligned_wrapped_vggt as PA
     dev = torch.device("cuda:0")
     B, S, ov = 1, args.frames, args.overlap
     enc, prev, gt = make_chunk(PA, B, S, ov, dev)
     win = args.seconds * 1e3 / args.rounds
+    if args.compose:
+        return compose_only(enc, prev, B, S, ov, dev, args.rounds, win)
     knob = os.environ.get("VGGT_POSE")
 
     def align(mode, use_gt):

@@ -10,6 +10,9 @@ them.  A plain module: no tests, no fixtures.
                output ulp for bf16)
   _model_rule  the kernel's worst row (||got - ref64||_2 over the RMS row norm of ref64) must be
                <= 2 x that of the documented fp32 arithmetic restated in plain torch on the host
+  _svd_centres, _centre_poses, _svd_pair_check
+               one 3x3 Umeyama problem for the two kernels that share csrc/small_eig.h's SVD
+               (test_gpu_geometry_edges.py, test_gpu_training_metrics.py)
 u = 2^-24, gamma_n = n u / (1 - n u)."""
 import math
 
@@ -167,6 +170,75 @@ def _figures(prefix):
     for k in sorted(FIG, key=str):
         if str(k[-1]).startswith(prefix) or str(k[0]).startswith(prefix):
             print("figure", k, FIG[k])
+
+
+# ------------------------------------------------------------------ one 3x3 problem for the two users of the shared SVD
+def _umeyama_torch(x, y, dt):
+    """Umeyama's closed form with unit weights on centres x -> y [n, 3] in `dt` arithmetic with LAPACK's SVD
+    (fp64: the reference, fp32: the model): R, t, c."""
+    x, y = x.to(dt), y.to(dt)
+    mx, my = x.mean(0), y.mean(0)
+    xc, yc = x - mx, y - my
+    Uu, sv, Vh = torch.linalg.svd(yc.T @ xc / x.shape[0])
+    D = torch.tensor([1.0, 1.0, -1.0 if float(torch.det(Uu @ Vh)) < 0 else 1.0], dtype=dt)
+    R = Uu @ torch.diag(D) @ Vh
+    c = (sv * D).sum() / (xc ** 2).sum(1).mean()
+    return R, my - c * (R @ mx), c
+
+
+def _svd_centres(kind):
+    """Camera centres x -> y (fp32 [S, 3]) that vggt_irls_sim3 takes as a point cloud with unit weights and
+    vggt_gt_pose_align as poses (_centre_poses), so that both solve the same 3x3 problem.
+      general  S = 5 in general position (spreads 3 : 2 : 1), y = 1.7 R0 x + t0 + noise.  The seed is chosen from the
+               host alone: the fp32 model's error is at least 3 x one fp32 rounding of the fp64 result on R, t and c,
+               so the 2 x model rule is not decided by a model that happens to be exact.
+      line     S = 3 collinear (rank 1), every number exact in fp32: y = 2 R0 x + t0 with R0 a quarter turn about z."""
+    if kind == "line":
+        x = torch.tensor([0.5, -0.25, 6.0]) + torch.tensor([[-1.5], [0.25], [2.0]]) * torch.tensor([1.0, -2.0, 2.0])
+        R0 = torch.tensor([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+        return x, 2.0 * x @ R0.T + torch.tensor([0.5, -1.0, 2.0])
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(5, 3, generator=g, dtype=F64) * torch.tensor([3.0, 2.0, 1.0], dtype=F64)).float()
+    i, j, k, r = (torch.tensor([0.3, -0.2, 0.5, 0.8], dtype=F64) / math.sqrt(1.02)).tolist()
+    R0 = torch.tensor([[1 - 2 * (j * j + k * k), 2 * (i * j - k * r), 2 * (i * k + j * r)],
+                       [2 * (i * j + k * r), 1 - 2 * (i * i + k * k), 2 * (j * k - i * r)],
+                       [2 * (i * k - j * r), 2 * (j * k + i * r), 1 - 2 * (i * i + j * j)]], dtype=F64)
+    y = 1.7 * x.double() @ R0.T + torch.tensor([0.4, -1.0, 2.0], dtype=F64) + 0.05 * torch.randn(5, 3, generator=g, dtype=F64)
+    return x, y.float()
+
+
+def _centre_poses(x, y):
+    """(pose_enc (1, S, 9), gt_extr (1, S, 3, 4)) whose camera centres -R^T t are exactly x and y: identity rotations
+    (the quaternion (0, 0, 0, 1) gives R = I exactly), t = -centre."""
+    S = x.shape[0]
+    enc = torch.cat([-x, torch.tensor([0.0, 0.0, 0.0, 1.0, 1.0, 1.0]).expand(S, 6)], -1)
+    extr = torch.cat([torch.eye(3).expand(S, 3, 3), -y[..., None]], -1)
+    return enc[None].contiguous(), extr[None].contiguous()
+
+
+def _svd_pair_check(errs, who, kind, R, t, c):
+    """One user's R [3, 3], t [3], c [] (host fp32) on _svd_centres(kind).  general: _model_rule against the one fp64
+    solve.  line: the rotation about the line is free, so R is a proper rotation (det = 1 and R^T R = I within 1e-6:
+    the fp32 rounding of an orthogonal matrix moves them by at most 6 u and 4 u) that maps the line onto the line
+    (R d = R0 d within 1e-6: the rounding of R moves R d by at most sqrt(3) u), and c = 2 within 2 u c."""
+    x, y = _svd_centres(kind)
+    if kind == "general":
+        Rr, tr, cr = _umeyama_torch(x, y, F64)
+        Rm, tm, cm = _umeyama_torch(x, y, F32)
+        _model_rule(errs, f"{who} R", R, Rm, Rr, "svd_pair")
+        _model_rule(errs, f"{who} t", t.reshape(1, 3), tm.reshape(1, 3), tr.reshape(1, 3), "svd_pair")
+        _model_rule(errs, f"{who} c", c.reshape(1, 1), cm.reshape(1, 1), cr.reshape(1, 1), "svd_pair")
+        return
+    Rd = R.double()
+    d = torch.tensor([1.0, -2.0, 2.0], dtype=F64) / 3.0
+    figures = {"det": (abs(float(torch.det(Rd)) - 1.0), 1e-6),
+               "RtR": (float((Rd.T @ Rd - torch.eye(3, dtype=F64)).abs().max()), 1e-6),
+               "line": (float((Rd @ d - torch.tensor([2.0, 1.0, 2.0], dtype=F64) / 3.0).abs().max()), 1e-6),
+               "c": (abs(float(c) - 2.0), 4 * U)}
+    print(f"svd pair {who} {kind}: {figures}")
+    for name, (v, bound) in figures.items():
+        if not v <= bound:
+            errs.append(f"{who} {kind}: {name} {v:.3e} > {bound:.3e}")
 
 
 # ------------------------------------------------------------------ dense outputs between sentinel guards

@@ -69,7 +69,7 @@ import pytest
 import torch
 
 from edge_rules import (ERR_ALIGN, ERR_SHAPE, F32, F64, NAN, OK, SENT, U, _bits, _done, _eq_bits, _fig, _figures, _gam,
-                        _gen, _model_rule, _within)
+                        _gen, _model_rule, _svd_centres, _svd_pair_check, _within)
 
 pytestmark = pytest.mark.gpu
 
@@ -339,6 +339,19 @@ def test_solve_rank_one(N, kind, n):
     if not rms <= rho + rnd:
         errs.append(f"{tag}: weighted RMS residual {rms:.3e} > {rho + rnd:.3e}")
     _done(errs, (tag, _reach_pass(n)))
+
+
+@pytest.mark.parametrize("kind", ["general", "line"])
+def test_solve_shares_its_svd_with_the_pose_alignment(N, kind):
+    """irls_solve's half of the pair that csrc/small_eig.h serves (the other half, on the same centres:
+    test_gpu_training_metrics.py::test_pose_sim3_shares_its_svd_with_the_point_alignment).  Unit weights, conf_dst
+    NULL, max_iters = 0: one solve.  The sums feeding the two solvers are reduced differently, so each is held to
+    the fp64 solve, not to the other."""
+    errs = []
+    x, y = _svd_centres(kind)
+    R, t, s = _irls(N, errs, f"svd pair {kind}", [x], [y], [torch.ones(x.shape[0])])
+    _svd_pair_check(errs, "irls_sim3", kind, R[0], t[0], s[0])
+    _done(errs)
 
 
 def test_solve_one_point(N):

@@ -92,6 +92,26 @@ def test_kth_value_matches_torch_kthvalue(N, n, pattern):
                     assert _bits(got) == _bits(want), (n, k, pattern, got, want)
 
 
+def test_kth_value_lands_on_a_zero_before_a_nan_tail(N):
+    """n = 257 (one workgroup plus one element): 100 negatives, 60 zeros of both signs, 57 positives, 40 NaN.  The
+    ranks 101 .. 160 land on a zero whatever its sign (-0 == +0 in torch.kthvalue's order, here on the same device
+    tensor), and the select returns it as +0; the ranks next to them and the NaN tail are torch's bit for bit."""
+    g = np.random.default_rng(257)
+    zeros = np.where(np.arange(60) % 2 == 0, np.float32(-0.0), np.float32(0.0))
+    x = np.concatenate([-1.0 - g.random(100), zeros, 1e-40 + g.random(57), np.full(40, NAN)]).astype(np.float32)
+    xg = torch.from_numpy(g.permutation(x)).cuda()
+    assert xg.numel() == 257
+    for k in (100, 101, 130, 160, 161, 217, 218, 257):
+        want = torch.kthvalue(xg, k).values.cpu().numpy()
+        got = N.kth_value(xg, k).cpu().numpy()
+        if k > 217:
+            assert np.isnan(want) and np.isnan(got), (k, got, want)
+        elif 101 <= k <= 160:
+            assert want == 0 and _bits(got) == 0, (k, got, want)
+        else:
+            assert _bits(got) == _bits(want), (k, got, want)
+
+
 def test_kth_value_rejects_bad_ranks_and_cpu(N):
     x = torch.arange(5, dtype=torch.float32)
     with pytest.raises(RuntimeError, match="HIP devices only"):

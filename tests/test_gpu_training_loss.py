@@ -56,6 +56,8 @@ def _edge_inputs():
     g = torch.Generator().manual_seed(8)
     pick = lambda p: torch.rand(shape, generator=g) < p  # noqa: E731
     conf[0, 1] = 0.0                      # a frame whose confidences are all 0: clamp_min(1e-8) of the amax
+    conf[1, 0] = -0.0                     # all -0: torch.amax gives -0 (the amax key keeps the zeros apart)
+    assert bool(mask[1, 0].any())
     pred[pick(0.02)] = 1e-9               # below the clamp
     pred[pick(0.01)] = 0.0
     pred[pick(0.01)] = -1.5
@@ -149,6 +151,9 @@ def test_values_stage_against_fp64(N):
         pred, conf, gt, mask = (t.cuda() for t in _inputs(key))
         val, amax, n = _values_raw(N, pred, conf, gt, mask)
         _check_values(key, val.cpu(), amax.cpu(), int(n))
+        if key == "edge":  # the all -0 frame: torch.amax's -0 (checked here on the CPU), bit for bit
+            assert int(_bits(torch.full((518,), -0.0).amax())) == -0x80000000
+            assert int(_bits(amax)[1, 0]) == -0x80000000 and int(_bits(amax)[0, 1]) == 0
         if key == "big":
             continue
         # the element-by-element path (pointers 4 bytes off a 16-byte boundary): the same bits

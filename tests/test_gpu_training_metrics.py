@@ -55,7 +55,8 @@ import numpy as np
 import pytest
 import torch
 
-from edge_rules import ERR_UNSUPPORTED, U, _done, _eq_bits, _raises, _within
+from edge_rules import (ERR_UNSUPPORTED, U, _centre_poses, _done, _eq_bits, _raises, _svd_centres, _svd_pair_check,
+                        _within)
 
 pytestmark = pytest.mark.gpu
 
@@ -224,6 +225,19 @@ def test_pose_sim3_vs_fp64(N, S, B, mirror):
         _eq_bits(errs, f"alias enc W={W}", alias.cpu(), got)
         _eq_bits(errs, f"alias T W={W}", T2.cpu(), Th)
         _eq_bits(errs, f"alias c W={W}", sc2.cpu(), sc.cpu())
+    _done(errs)
+
+
+@pytest.mark.parametrize("kind", ["general", "line"])
+def test_pose_sim3_shares_its_svd_with_the_point_alignment(N, kind):
+    """umeyama3's half of the pair that csrc/small_eig.h serves (the other half, on the same centres:
+    test_gpu_geometry_edges.py::test_solve_shares_its_svd_with_the_pose_alignment): the centres as poses with
+    identity rotations, Sim(3) mode."""
+    errs = []
+    enc, extr = _centre_poses(*_svd_centres(kind))
+    sc, T, _ = N.gt_pose_align(enc.to(DEV), extr.to(DEV), N.GT_POSE_SIM3)
+    Th = T.cpu()[0]
+    _svd_pair_check(errs, "gt_pose_align", kind, Th[:3, :3].contiguous(), Th[:3, 3].contiguous(), sc.cpu()[0])
     _done(errs)
 
 
