@@ -420,6 +420,11 @@ int vggt_layernorm_grouped(const void* x, int in_dtype, int64_t ldx, const float
  * decoder (alignment_head.py:463,475,534-538, cross blocks, gated_update.py:22-36).
  * A, W and out may be any 4-byte aligned row-major views: 16-byte loads are used when K, lda, ldw
  * are multiples of 4 and A and W are 16-byte aligned, scalar loads otherwise (the same sums).
+ *
+ * One check for the three entries (vggt_linear_f32, _ws, _grouped), in this order: M, N or K < 1, A, W or
+ * out NULL, (grouped) M > 256 or groups outside [1, 65535], (not grouped) VGGT_EPI_RESID_F32 without gamma:
+ * VGGT_ERR_SHAPE; then act_in not 0 / 1, an epi other than the three above, (grouped) VGGT_EPI_RESID_F32:
+ * VGGT_ERR_UNSUPPORTED.  bias may be NULL.  Nothing is launched by a refused call.
  */
 int vggt_linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N, int K,
                     int act_in, int epi, float* out, int64_t ldo, const float* gamma, void* stream);
@@ -446,7 +451,8 @@ int vggt_linear_f32_grouped(const float* A, int64_t lda, int64_t a_gstride, cons
  *         ([B*Nt, 3D]) and g_in[:, D:2D] = |update_b| memory[b, i]  ([B*Nt, 2D]);
  *   diff: g_in[:, 0:D] = deltas - memory;
  *   tail: out = normalize(memory + sigmoid(logit) normalize(diff - (diff . memory) memory))
- *         with F.normalize's max(|x|, 1e-12). */
+ *         with F.normalize's max(|x|, 1e-12).
+ * A size < 1 or a NULL pointer: VGGT_ERR_SHAPE. */
 int vggt_gated_update_prep(const float* memory, const float* update, int B, int Nt, int D, float* inp, float* g_in,
                            void* stream);
 int vggt_gated_update_diff(const float* memory, const float* deltas, int rows, int D, float* g_in, void* stream);
@@ -459,6 +465,40 @@ int vggt_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw,
                        void* stream);
 
 /*
+ * Which kernel the linear entries launch: what linear_resolve, the dispatcher the entries themselves call,
+ * answers for these shapes under the current VGGT_TUNE_LINEAR_* knobs.  Host arithmetic only (no device
+ * needed).  groups == 0 asks about vggt_linear_f32_ws with a scratch of ws_bytes (0: none, i.e.
+ * vggt_linear_f32) and gamma given or not; any other value asks about vggt_linear_f32_grouped with that many
+ * groups (has_gamma and ws_bytes unused).  Returns what the entry would return for non-NULL A, W and out.
+ * The rule:
+ *   grouped, or M <= 256 with VGGT_TUNE_LINEAR_WK > 0: FAMILY_WK, kw = 2, doubled up to 8 while K > kw * WK
+ *     (64 when grouped with the knob at 0) waves of a workgroup on k ranges of kchunk = roundup(ceil(K / kw), 64),
+ *     mt = 1 (M <= 16) or 4 accumulator tiles per wave, grid (ceil(N / 16), ceil(M / 64), groups), 64 kw threads;
+ *   else splits = 1, doubled up to VGGT_LINEAR_F32_MAX_SPLITS while blocks * splits * 2 <= 512 (blocks =
+ *     ceil(N / 64) ceil(M / 64)) and K / (2 splits) >= VGGT_TUNE_LINEAR_SPLIT_K, then halved until the scratch
+ *     holds the counters and `splits` slabs of roundup(M, 64) x N floats:
+ *     splits == 1: FAMILY_BLOCK, kchunk = K; else FAMILY_SPLIT, kchunk = roundup(ceil(K / splits), 16) and
+ *     one_launch = 1 when blocks <= VGGT_LINEAR_F32_WS_COUNTERS and VGGT_TUNE_LINEAR_ONE_LAUNCH (the tile's
+ *     last block combines), 0 for a second launch of linear_f32_reduce over min(ceil(M N / 256), 4096) groups;
+ *     grid (ceil(N / 64), ceil(M / 64), splits), 256 threads.
+ * No kernel uses dynamic LDS.
+ */
+#define VGGT_LINEAR_FAMILY_WK 0    /* linear_f32_wk_kernel<kw, mt, act_in, epi>: K split inside the workgroup */
+#define VGGT_LINEAR_FAMILY_BLOCK 1 /* linear_f32_kernel<act_in, epi>, K not split                             */
+#define VGGT_LINEAR_FAMILY_SPLIT 2 /* linear_f32_kernel<act_in, epi>, K split over blockIdx.z                 */
+typedef struct {
+  int family;      /* VGGT_LINEAR_FAMILY_* */
+  int kw, mt;      /* FAMILY_WK: waves along K, accumulator tiles per wave (else 0, 4) */
+  int splits;      /* FAMILY_SPLIT: K ranges over workgroups (else 1) */
+  int kchunk;      /* k per wave (FAMILY_WK) or per split; K when nothing splits */
+  int one_launch;  /* 0: FAMILY_SPLIT followed by linear_f32_reduce */
+  int grid[3], threads;
+  int rc;          /* VGGT_OK, or the entry point's error */
+} vggt_linear_f32_form_t;
+int vggt_linear_f32_form(int M, int N, int K, int act_in, int epi, int groups, int has_gamma, size_t ws_bytes,
+                         vggt_linear_f32_form_t* form);
+
+/*
  * Small-window attention (nk <= 128, D <= 256), one wave per (batch, head),
  * f32 softmax; dtype VGGT_DTYPE_BF16 or VGGT_DTYPE_F32 for all of q/k/v/o.
  * Layout as vggt_attention_fwd (v shares k's batch stride).  Replaces the SDPA
@@ -469,19 +509,49 @@ int vggt_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw,
  * (fp32 scores, P rounded to bf16 for P.V, as the reference's bf16 SDPA) unless
  * dtype carries VGGT_ATTN_SMALL_EXACT: the training forward, whose backward
  * (vggt_attention_small_bwd) recomputes P in fp32 from the same formula.
+ * batch, heads, nq, nk or D < 1, nk > 128, D > 256, (2 nk (D + 1) + D) 4 bytes over 160 KiB, or q, k, v or o
+ * NULL: VGGT_ERR_SHAPE; then a dtype that is neither: VGGT_ERR_UNSUPPORTED.
  */
 #define VGGT_ATTN_SMALL_EXACT 0x100
 int vggt_attention_small(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk, int64_t k_bstride,
                          const void* v, int64_t ldv, void* o, int64_t ldo, int64_t o_bstride, int dtype, int batch,
                          int heads, int nq, int nk, int D, float scale, void* stream);
 
+/*
+ * Which kernel vggt_attention_small launches: what attn_small_resolve, the dispatcher the entry itself calls,
+ * answers.  Host arithmetic only.  dtype as the entry's (with or without VGGT_ATTN_SMALL_EXACT); ptr_align: the
+ * largest power of two, in bytes, that divides all four base pointers (the entry caps it at 256).  Returns what
+ * the entry would return for non-NULL pointers.  The rule, after the entry's checks:
+ *   bf16 without EXACT, nq <= 16, nk <= 16, D % 16 == 0, all four leading dimensions % 4 == 0, ptr_align % 8 == 0
+ *     and VGGT_ATTN_SMALL_MFMA (environment, default 1) nonzero: FAMILY_MFMA, dt = D for 64 / 128 (compile-time D)
+ *     else 0, ceil(batch heads / 4) workgroups of 256 threads, 128 D bytes of LDS;
+ *   else, with VGGT_ATTN_SMALL_WG (environment, default 1) nonzero, while ((nq + nk)(D + 1) + nk D + nq nk) 4
+ *     <= 64 KiB: FAMILY_WG, batch heads workgroups of 256 threads and that much LDS;
+ *   else FAMILY_WAVE: batch heads workgroups of 64 threads, (2 nk (D + 1) + D) 4 bytes of LDS.
+ */
+#define VGGT_ATTN_SMALL_FAMILY_MFMA 0 /* attn_small_mfma_kernel<dt>   */
+#define VGGT_ATTN_SMALL_FAMILY_WG 1   /* attn_small_wg_kernel<dtype>  */
+#define VGGT_ATTN_SMALL_FAMILY_WAVE 2 /* attn_small_kernel<dtype>     */
+typedef struct {
+  int family;             /* VGGT_ATTN_SMALL_FAMILY_* */
+  int dt;                 /* FAMILY_MFMA: the compile-time D (64, 128), 0 for a runtime D */
+  int grid, threads, lds; /* workgroups, threads per workgroup, dynamic LDS bytes */
+  int rc;                 /* VGGT_OK, or the entry point's error */
+} vggt_attention_small_form_t;
+int vggt_attention_small_form(int dtype, int nq, int nk, int D, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                              int ptr_align, int batch, int heads, vggt_attention_small_form_t* form);
+
 /* fp32 variant of vggt_headnorm_rope (decoder / camera head run in fp32): D a multiple of 4 up to
- * 1024, any col_off (scalar loads); positions clamped and b ignored without w as there. */
+ * 1024, any col_off (scalar loads); positions clamped and b ignored without w as there.  M == 0: VGGT_OK,
+ * nothing launched; M < 0, H < 1, D out of range, buf NULL, or a rope_mode other than VGGT_ROPE_NONE without
+ * pos, cos_tab, sin_tab, period > 0 and tab_len > 0: VGGT_ERR_SHAPE; then an unknown rope_mode:
+ * VGGT_ERR_UNSUPPORTED. */
 int vggt_headnorm_rope_f32(float* buf, int64_t ld, int col_off, int M, int H, int D, const float* w, const float* b,
                            float eps, int rope_mode, const int32_t* pos, int period, const float* cos_tab,
                            const float* sin_tab, int tab_len, void* stream);
 
-/* y_bf16[r, c] = bf16(x_f32[r, c])  (autocast input cast of a Linear). */
+/* y_bf16[r, c] = bf16(x_f32[r, c])  (autocast input cast of a Linear).  rows < 0, cols, ldx or ldy % 4, x or y
+ * NULL with rows > 0: VGGT_ERR_SHAPE; x off 16 bytes or y off 8: VGGT_ERR_ALIGN. */
 int vggt_cast_f32_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int rows, int cols, void* stream);
 
 /*

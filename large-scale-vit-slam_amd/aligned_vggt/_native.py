@@ -58,6 +58,8 @@ _SIGS = {
     "vggt_attention_stamps_form": [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)],
     "vggt_gemm_form": [_i] * 11 + [_i64] * 4 + [_i] * 3 + [_vp],
     "vggt_conv_form": [_i] * 13 + [_i64] * 3 + [_i, _vp],
+    "vggt_linear_f32_form": [_i] * 7 + [ctypes.c_size_t, _vp],
+    "vggt_attention_small_form": [_i] * 4 + [_i64] * 4 + [_i] * 3 + [_vp],
     "vggt_patch_im2col": [_vp, _i, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _i, _vp],
     "vggt_dino_assemble": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "vggt_special_tokens": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp],
@@ -640,6 +642,56 @@ def gated_update_tail(memory: torch.Tensor, deltas: torch.Tensor, logit: torch.T
     assert out.is_contiguous() and out.numel() == rows * D
     _check(lib().vggt_gated_update_tail(_p(memory), _p(deltas), _p(logit), rows, D, _p(out), _stream()),
            "vggt_gated_update_tail")
+
+
+LINEAR_FAMILY = ("in-workgroup split", "block, no split", "cross-workgroup split")
+_LINEAR_FORM_FIELDS = ("family", "kw", "mt", "splits", "kchunk", "one_launch", "grid_x", "grid_y", "grid_z", "threads",
+                       "rc")
+
+
+class _LinearForm(ctypes.Structure):
+    _fields_ = [(name, _i) for name in _LINEAR_FORM_FIELDS]
+
+
+def linear_f32_form(M: int, N: int, K: int, act_in: int = 0, epi: int = EPI_F32, groups: int = 0,
+                    has_gamma: bool = True, ws_bytes: Optional[int] = None) -> dict:
+    """vggt_linear_f32_form (host arithmetic only): the kernel linear_f32 (groups == 0; ws_bytes None: the
+    scratch linear_f32 passes) or linear_f32_grouped (any other `groups`) launches for this shape under the
+    current TUNE_LINEAR_* knobs, as a dict of vggt_linear_f32_form_t's fields plus "grid" and "name" (the
+    family); "rc" is the entry point's return code."""
+    if ws_bytes is None:
+        ws_bytes = 4 * (LINEAR_F32_WS_COUNTERS + LINEAR_F32_MAX_SPLITS * ((M + 63) // 64) * 64 * N) if M <= 256 else 0
+    f = _LinearForm()
+    lib().vggt_linear_f32_form(M, N, K, act_in, epi, groups, int(has_gamma), max(ws_bytes, 0), ctypes.byref(f))
+    d = {name: getattr(f, name) for name in _LINEAR_FORM_FIELDS}
+    d["grid"] = (f.grid_x, f.grid_y, f.grid_z)
+    d["name"] = LINEAR_FAMILY[f.family] if f.rc == VGGT_OK else None
+    return d
+
+
+ATTN_SMALL_FAMILY = ("mfma", "workgroup", "one-wave")
+_ATTN_SMALL_FORM_FIELDS = ("family", "dt", "grid", "threads", "lds", "rc")
+
+
+class _AttnSmallForm(ctypes.Structure):
+    _fields_ = [(name, _i) for name in _ATTN_SMALL_FORM_FIELDS]
+
+
+def attention_small_form(dtype: int, nq: int, nk: int, D: int, batch: int = 1, heads: int = 1,
+                         ldq: Optional[int] = None, ldk: Optional[int] = None, ldv: Optional[int] = None,
+                         ldo: Optional[int] = None, ptr_align: int = 16, exact: bool = False) -> dict:
+    """vggt_attention_small_form (host arithmetic only): the kernel attention_small launches for this window
+    under the process's VGGT_ATTN_SMALL_MFMA / _WG, as a dict of vggt_attention_small_form_t's fields plus
+    "name" (the family); "rc" is the entry point's return code.  dtype: DTYPE_*; dense leading dimensions
+    (heads * D) unless given; ptr_align: the bytes all four base pointers are aligned to."""
+    f = _AttnSmallForm()
+    ld = heads * D
+    lib().vggt_attention_small_form(dtype | (ATTN_SMALL_EXACT if exact else 0), nq, nk, D, ld if ldq is None else ldq,
+                                    ld if ldk is None else ldk, ld if ldv is None else ldv, ld if ldo is None else ldo,
+                                    ptr_align, batch, heads, ctypes.byref(f))
+    d = {name: getattr(f, name) for name in _ATTN_SMALL_FORM_FIELDS}
+    d["name"] = ATTN_SMALL_FAMILY[f.family] if f.rc == VGGT_OK else None
+    return d
 
 
 _SPLIT_WS = {}

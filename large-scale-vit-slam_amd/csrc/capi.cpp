@@ -53,6 +53,7 @@ const GemmKnobs g_vggt_gemm_knobs = {env_or("VGGT_GEMM_MID", 0),   env_or("VGGT_
                                      env_or("VGGT_GEMM_BM", 0),    env_or("VGGT_GEMM_FULLK", 5),
                                      env_or("VGGT_GEMM_GM", 4) & 255, env_or("VGGT_GEMM_SPLITDMA", 1) != 0,
                                      env_or("VGGT_HEADNORM_TILE", -1)};
+const SmallKnobs g_vggt_small_knobs = {env_or("VGGT_ATTN_SMALL_MFMA", 1), env_or("VGGT_ATTN_SMALL_WG", 1)};
 // key-split tail of the global attention launch (attention.hip, vggt_attention_fwd_ws): 0 the slot-model plan,
 // -1 off (bitwise the unsplit launch), parts | tail_blocks << 8 forced over the launch's last units, the same with
 // VGGT_ATTN_TAIL_SPLIT_PER_ELEMENT over every batch element's last units (tests, A/B).  On by default: the plan is

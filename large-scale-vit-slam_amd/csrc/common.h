@@ -216,6 +216,12 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
 
+// Workgroups of 256 threads for a grid-stride pass over `total` elements: one thread each, at most `cap` groups
+inline int grid_for(int64_t total, int cap) {
+  const int64_t g = (total + 255) / 256;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
 #define HIP_LAUNCH_CHECK()                         \
   do {                                             \
     hipError_t e_ = hipGetLastError();             \

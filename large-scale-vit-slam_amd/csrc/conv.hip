@@ -606,10 +606,7 @@ __global__ __launch_bounds__(256) void dpt_act_kernel(const float* __restrict__ 
   }
 }
 
-inline int grid_for(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
-}
+constexpr int kMaxBlocks = 16384;  // of the elementwise kernels below
 
 }  // namespace
 
@@ -791,7 +788,7 @@ extern "C" int vggt_split_act_bf16x2(const float* x, int64_t ldx, int64_t rows, 
   if (rows < 0 || cols <= 0 || cols % 4 || ldx < cols) return VGGT_ERR_SHAPE;
   if ((ldx % 4) || ((uintptr_t)x % 16) || ((uintptr_t)hi % 8) || ((uintptr_t)lo % 8)) return VGGT_ERR_ALIGN;
   if (rows == 0) return VGGT_OK;
-  split_act_kernel<<<grid_for(rows * (cols / 4)), 256, 0, (hipStream_t)stream>>>(x, ldx, rows, cols, relu,
+  split_act_kernel<<<grid_for(rows * (cols / 4), kMaxBlocks), 256, 0, (hipStream_t)stream>>>(x, ldx, rows, cols, relu,
                                                                               (bf16_t*)hi, (bf16_t*)lo);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
@@ -800,7 +797,7 @@ extern "C" int vggt_split_act_bf16x2(const float* x, int64_t ldx, int64_t rows, 
 extern "C" int vggt_split_bf16x2(const float* x, int64_t n, void* hi, void* lo, void* stream) {
   if (n < 0) return VGGT_ERR_SHAPE;
   if (n == 0) return VGGT_OK;
-  split_bf16x2_kernel<<<grid_for(n), 256, 0, (hipStream_t)stream>>>(x, n, (bf16_t*)hi, (bf16_t*)lo);
+  split_bf16x2_kernel<<<grid_for(n, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(x, n, (bf16_t*)hi, (bf16_t*)lo);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -812,7 +809,7 @@ static int upsample_launch(const float* x, int nimg, int hi, int wi, int C, int 
                            uintptr_t a16, void* stream) {
   if (nimg <= 0 || hi <= 0 || wi <= 0 || ho <= 0 || wo <= 0 || C % cmod || !shape_ok) return VGGT_ERR_SHAPE;
   if (a16 % 16 || ((uintptr_t)y_hi | (uintptr_t)y_lo) % 8) return VGGT_ERR_ALIGN;
-  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4)), 256, 0, (hipStream_t)stream>>>(
+  upsample_kernel<<<grid_for((int64_t)nimg * ho * wo * (C / 4), kMaxBlocks), 256, 0, (hipStream_t)stream>>>(
       x, nimg, hi, wi, C, y, ho, wo, pos, (bf16_t*)y_hi, (bf16_t*)y_lo, split_relu, pos_sep);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
@@ -841,7 +838,7 @@ extern "C" int vggt_upsample_bilinear_split_sep(const float* x, int nimg, int hi
 extern "C" int vggt_dpt_activate(const float* x, int64_t ldx, int64_t npix, int pix_per_img, int ncl, int act,
                                  const float* scale, float* pts, float* conf, void* stream) {
   if (npix <= 0 || ncl < 2 || pix_per_img <= 0 || (act != 0 && act != 1)) return VGGT_ERR_SHAPE;
-  dpt_act_kernel<<<grid_for(npix), 256, 0, (hipStream_t)stream>>>(x, ldx, npix, pix_per_img, ncl, act, scale, pts,
+  dpt_act_kernel<<<grid_for(npix, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(x, ldx, npix, pix_per_img, ncl, act, scale, pts,
                                                                   conf);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;

@@ -100,10 +100,7 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const float* __restrict_
   }
 }
 
-inline int grid_for(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
+constexpr int kMaxBlocks = 8192;
 
 }  // namespace
 
@@ -112,7 +109,7 @@ extern "C" int vggt_patch_im2col(const float* images, int F, int H, int W, int p
   if (F <= 0 || patch <= 0 || H % patch || W % patch || Kp % 8 || Kp < 3 * patch * patch) return VGGT_ERR_SHAPE;
   if ((uintptr_t)A % 16) return VGGT_ERR_ALIGN;
   const int64_t total = (int64_t)F * (H / patch) * (W / patch) * (Kp / 8);
-  im2col_kernel<<<grid_for(total), 256, 0, (hipStream_t)stream>>>(images, F, H, W, patch, mean[0], mean[1], mean[2],
+  im2col_kernel<<<grid_for(total, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(images, F, H, W, patch, mean[0], mean[1], mean[2],
                                                                    std_[0], std_[1], std_[2],
                                                                    (bf16_t*)A, Kp);
   HIP_LAUNCH_CHECK();
@@ -124,7 +121,7 @@ extern "C" int vggt_dino_assemble(const void* patch, const float* cls, const flo
   if (F <= 0 || hw <= 0 || nreg < 0 || C % 4) return VGGT_ERR_SHAPE;
   if (((uintptr_t)patch | (uintptr_t)cls | (uintptr_t)reg | (uintptr_t)pos | (uintptr_t)x) % 16) return VGGT_ERR_ALIGN;
   const int64_t total = (int64_t)F * (1 + nreg + hw) * (C / 4);
-  dino_assemble_kernel<<<grid_for(total), 256, 0, (hipStream_t)stream>>>((const bf16_t*)patch, cls, reg, pos, F, hw,
+  dino_assemble_kernel<<<grid_for(total, kMaxBlocks), 256, 0, (hipStream_t)stream>>>((const bf16_t*)patch, cls, reg, pos, F, hw,
                                                                           nreg, C, x);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
@@ -135,7 +132,7 @@ extern "C" int vggt_special_tokens(float* x, int64_t ldx, int F, int S, int P, i
   if (F <= 0 || S <= 0 || n <= 0 || n > P || C % 4 || ldx % 4) return VGGT_ERR_SHAPE;
   if (((uintptr_t)x | (uintptr_t)tok) % 16) return VGGT_ERR_ALIGN;
   const int64_t total = (int64_t)F * n * (C / 4);
-  special_tokens_kernel<<<grid_for(total), 256, 0, (hipStream_t)stream>>>(x, ldx, F, S, P, n, C, tok);
+  special_tokens_kernel<<<grid_for(total, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(x, ldx, F, S, P, n, C, tok);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
@@ -145,7 +142,7 @@ extern "C" int vggt_copy_rows_f32(const float* src, int64_t lds, float* dst, int
   if (rows < 0 || cols % 4 || lds % 4 || ldd % 4) return VGGT_ERR_SHAPE;
   if (((uintptr_t)src | (uintptr_t)dst) % 16) return VGGT_ERR_ALIGN;
   if (rows == 0 || cols == 0) return VGGT_OK;
-  copy_rows_kernel<<<grid_for((int64_t)rows * cols / 4), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols);
+  copy_rows_kernel<<<grid_for((int64_t)rows * cols / 4, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }

@@ -4,7 +4,8 @@
 // camera-head attention over <= 128 tokens), fp32 QK-norm + RoPE, casts and
 // row-remapped LayerNorm.  See include/vggt_mi355x.h for the contracts.
 #include <math.h>
-#include <stdlib.h>
+
+#include <utility>
 
 #include "common.h"
 #include "tune.h"
@@ -110,6 +111,45 @@ __device__ __forceinline__ void wave_linear_f32(const float* __restrict__ A, int
   }
 }
 
+// The one epilogue of every form, for column n: v + bias[n], GELU, out += gamma[n] * v, store (in this
+// order; every form's bits are the others').  The column's two loads are taken once, ahead of a row loop.
+template <int EPI>
+struct LinearEpi {
+  float bv, g;
+  __device__ __forceinline__ LinearEpi(const float* bias, const float* gamma, int n)
+      : bv(bias ? bias[n] : 0.f), g(EPI == VGGT_EPI_RESID_F32 ? gamma[n] : 0.f) {}
+  __device__ __forceinline__ void operator()(float v, float* op) const {
+    v += bv;
+    if constexpr (EPI == VGGT_EPI_GELU_BF16) v = gelu_erf(v);  // GELU, f32 out
+    if constexpr (EPI == VGGT_EPI_RESID_F32) v = *op + g * v;
+    *op = v;
+  }
+};
+
+// Split-K combine of one output element: the partial slabs summed in split order, then the epilogue
+template <int EPI>
+__device__ __forceinline__ void linear_combine(const float* part, int splits, int64_t mstride, int64_t off, int n,
+                                               float* op, const float* bias, const float* gamma) {
+  float v = 0.f;
+  for (int z = 0; z < splits; ++z) v += part[z * mstride + off];
+  LinearEpi<EPI>(bias, gamma, n)(v, op);
+}
+
+// A lane's accumulator rows: acc[mt][i] belongs to row m = 16 mt + 4 q + i (q = lane >> 4) of the slab and
+// column n0 + (lane & 15); f(m, acc[mt][i]) for the rows below M.
+template <int MT, typename F>
+__device__ __forceinline__ void for_each_acc_row(const f32x4 (&acc)[MT], int mt_n, int q, int M, F f) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    if (mt >= mt_n) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = mt * 16 + 4 * q + i;
+      if (m < M) f(m, acc[mt][i]);
+    }
+  }
+}
+
 template <int ACT_IN, int EPI>
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ A, int64_t lda,
                                                          const float* __restrict__ W, int64_t ldw,
@@ -131,7 +171,6 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
   // `cnt` every wave takes part in the tile's last-block protocol)
   const bool active = n0 < N;
   if (!active && !cnt) return;
-  const int Mfull = M;
   const int mbase = blockIdx.y * 64;
   A += (int64_t)mbase * lda;
   out += (int64_t)mbase * ldo;
@@ -140,20 +179,11 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
   const int mt_n = (M + 15) / 16;
   f32x4 acc[4];
   wave_linear_f32<ACT_IN>(A, lda, W, ldw, M, N, K, n0, kbeg, kend, lane, acc);
-  // C[m = 16mt + 4q + i][n = n0 + r]
   const int n = n0 + r;
   if (part) {
     if (active && n < N) {
       float* pp = part + ((int64_t)blockIdx.z * gridDim.y * 64 + mbase) * N + n;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        if (mt >= mt_n) break;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m = mt * 16 + 4 * q + i;
-          if (m < M) pp[(int64_t)m * N] = acc[mt][i];
-        }
-      }
+      for_each_acc_row(acc, mt_n, q, M, [&](int m, float v) { pp[(int64_t)m * N] = v; });
     }
     if (!cnt) return;
     // this block's partials visible device-wide (every XCD's L2) before its ticket
@@ -171,36 +201,15 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
     for (int e = threadIdx.x; e < 64 * 64; e += 256) {
       const int m = e >> 6, nn = c0 + (e & 63);
       if (m >= M || nn >= N) continue;
-      const int64_t off = (int64_t)(mbase + m) * N + nn;
-      float v = 0.f;
-      for (int z = 0; z < (int)gridDim.z; ++z) v += part[z * mstride + off];
-      v += bias ? bias[nn] : 0.f;
-      float* op = out + (int64_t)m * ldo + nn;
-      if constexpr (EPI == VGGT_EPI_GELU_BF16) v = gelu_erf(v);
-      if constexpr (EPI == VGGT_EPI_RESID_F32) v = *op + gamma[nn] * v;
-      *op = v;
+      linear_combine<EPI>(part, gridDim.z, mstride, (int64_t)(mbase + m) * N + nn, nn, out + (int64_t)m * ldo + nn,
+                          bias, gamma);
     }
     if (threadIdx.x == 0) __hip_atomic_store(word, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    (void)Mfull;
     return;
   }
   if (n >= N) return;
-  const float bv = bias ? bias[n] : 0.f;
-  const float g = (EPI == VGGT_EPI_RESID_F32) ? gamma[n] : 0.f;
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    if (mt >= mt_n) break;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = mt * 16 + 4 * q + i;
-      if (m >= M) continue;
-      float v = acc[mt][i] + bv;
-      float* op = out + (int64_t)m * ldo + n;
-      if constexpr (EPI == VGGT_EPI_GELU_BF16) v = gelu_erf(v);  // GELU, f32 out
-      if constexpr (EPI == VGGT_EPI_RESID_F32) v = *op + g * v;
-      *op = v;
-    }
-  }
+  const LinearEpi<EPI> epi(bias, gamma, n);
+  for_each_acc_row(acc, mt_n, q, M, [&](int m, float v) { epi(v, out + (int64_t)m * ldo + n); });
 }
 
 // Skinny fp32 GEMM (M <= 256), split along K INSIDE the workgroup: KW waves
@@ -247,65 +256,8 @@ __global__ __launch_bounds__(64 * KW) void linear_f32_wk_kernel(const float* __r
   const int r = lane & 15, q = lane >> 4;
   const int n = n0 + r;
   if (n >= N) return;
-  const float bv = bias ? bias[n] : 0.f;
-  const float g = (EPI == VGGT_EPI_RESID_F32) ? gamma[n] : 0.f;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    if (mt >= mt_n) break;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = mt * 16 + 4 * q + i;
-      if (m >= M) continue;
-      float v = acc[mt][i] + bv;
-      float* op = out + (int64_t)m * ldo + n;
-      if constexpr (EPI == VGGT_EPI_GELU_BF16) v = gelu_erf(v);
-      if constexpr (EPI == VGGT_EPI_RESID_F32) v = *op + g * v;
-      *op = v;
-    }
-  }
-}
-
-template <int KW, int MT, int ACT_IN>
-void launch_linear_wk(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N, int K,
-                      int epi, float* out, int64_t ldo, const float* gamma, hipStream_t s, int groups = 1,
-                      int64_t a_gs = 0, int64_t w_gs = 0, int64_t b_gs = 0, int64_t o_gs = 0) {
-  // k ranges of whole 64-k steps (the vector loop), the last wave takes the rest
-  const int kchunk = ((K + KW - 1) / KW + 63) / 64 * 64;
-  const dim3 grid((N + 15) / 16, (M + 63) / 64, groups);
-  if (epi == VGGT_EPI_F32)
-    linear_f32_wk_kernel<KW, MT, ACT_IN, VGGT_EPI_F32><<<grid, 64 * KW, 0, s>>>(A, lda, W, ldw, bias, M, N, K, out, ldo, gamma, kchunk, a_gs, w_gs, b_gs, o_gs);
-  else if (epi == VGGT_EPI_GELU_BF16)
-    linear_f32_wk_kernel<KW, MT, ACT_IN, VGGT_EPI_GELU_BF16><<<grid, 64 * KW, 0, s>>>(A, lda, W, ldw, bias, M, N, K, out, ldo, gamma, kchunk, a_gs, w_gs, b_gs, o_gs);
-  else
-    linear_f32_wk_kernel<KW, MT, ACT_IN, VGGT_EPI_RESID_F32><<<grid, 64 * KW, 0, s>>>(A, lda, W, ldw, bias, M, N, K, out, ldo, gamma, kchunk, a_gs, w_gs, b_gs, o_gs);
-}
-
-// The in-workgroup split: each wave keeps ~g_vggt_linear_wk k (2..8 waves).  The
-// wave count depends on K only, so a row's result does not depend on M (a
-// grouped encode of three chunks gives each chunk's rows the bits of its own
-// encode); 64-row slabs along blockIdx.y, groups along blockIdx.z.
-void linear_wk_dispatch(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N,
-                        int K, int act_in, int epi, float* out, int64_t ldo, const float* gamma, hipStream_t s,
-                        int groups, int64_t a_gs, int64_t w_gs, int64_t b_gs, int64_t o_gs) {
-  const int mt = M <= 16 ? 1 : 4;
-  const int wk = g_vggt_linear_wk > 0 ? g_vggt_linear_wk : 64;
-  int kw = 2;
-  while (kw < 8 && K > kw * wk) kw *= 2;
-#define WK(KW_, MT_)                                                                                          \
-  (act_in ? launch_linear_wk<KW_, MT_, 1>(A, lda, W, ldw, bias, M, N, K, epi, out, ldo, gamma, s, groups, a_gs, \
-                                          w_gs, b_gs, o_gs)                                                     \
-          : launch_linear_wk<KW_, MT_, 0>(A, lda, W, ldw, bias, M, N, K, epi, out, ldo, gamma, s, groups, a_gs, \
-                                          w_gs, b_gs, o_gs))
-  if (mt == 1) {
-    if (kw == 2) WK(2, 1);
-    else if (kw == 4) WK(4, 1);
-    else WK(8, 1);
-  } else {
-    if (kw == 2) WK(2, 4);
-    else if (kw == 4) WK(4, 4);
-    else WK(8, 4);
-  }
-#undef WK
+  const LinearEpi<EPI> epi(bias, gamma, n);
+  for_each_acc_row(acc, mt_n, q, M, [&](int m, float v) { epi(v, out + (int64_t)m * ldo + n); });
 }
 
 // ------------------------------------------------------------------------
@@ -389,13 +341,7 @@ __global__ __launch_bounds__(256) void linear_f32_reduce(const float* __restrict
   const int64_t total = (int64_t)M * N;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int m = (int)(e / N), n = (int)(e % N);
-    float v = 0.f;
-    for (int z = 0; z < splits; ++z) v += part[z * mstride + e];
-    v += bias ? bias[n] : 0.f;
-    float* op = out + (int64_t)m * ldo + n;
-    if constexpr (EPI == VGGT_EPI_GELU_BF16) v = gelu_erf(v);
-    if constexpr (EPI == VGGT_EPI_RESID_F32) v = *op + gamma[n] * v;
-    *op = v;
+    linear_combine<EPI>(part, splits, mstride, e, n, out + (int64_t)m * ldo + n, bias, gamma);
   }
 }
 
@@ -412,6 +358,13 @@ template <typename T>
 __device__ __forceinline__ void st1(T* p, float v) {
   if constexpr (sizeof(T) == 2) *(bf16_t*)p = f2bf(v);
   else *(float*)p = v;
+}
+
+// One score of the two fp32 forms: q . k summed serially over d, then the scale
+__device__ __forceinline__ float attn_score(const float* qr, const float* kr, int D, float scale) {
+  float a = 0.f;
+  for (int d = 0; d < D; ++d) a = fmaf(qr[d], kr[d], a);
+  return a * scale;
 }
 
 template <typename T>
@@ -440,16 +393,8 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const T* __restrict__ q,
     for (int d = lane; d < D; d += 64) Qr[d] = ld1(qp + d);
     __syncthreads();
     float s0 = -INFINITY, s1 = -INFINITY;
-    if (lane < nk) {
-      float a = 0.f;
-      for (int d = 0; d < D; ++d) a = fmaf(Qr[d], Ks[lane * DP + d], a);
-      s0 = a * scale;
-    }
-    if (lane + 64 < nk) {
-      float a = 0.f;
-      for (int d = 0; d < D; ++d) a = fmaf(Qr[d], Ks[(lane + 64) * DP + d], a);
-      s1 = a * scale;
-    }
+    if (lane < nk) s0 = attn_score(Qr, Ks + lane * DP, D, scale);
+    if (lane + 64 < nk) s1 = attn_score(Qr, Ks + (lane + 64) * DP, D, scale);
     const float m = wave_max(fmaxf(s0, s1));
     const float p0 = lane < nk ? expf(s0 - m) : 0.f;
     const float p1 = lane + 64 < nk ? expf(s1 - m) : 0.f;
@@ -506,11 +451,7 @@ __global__ __launch_bounds__(256) void attn_small_wg_kernel(const T* __restrict_
   __syncthreads();
   for (int p = tid; p < nq * nk; p += 256) {
     const int i = p / nk, j = p % nk;
-    const float* qr = Qs + i * DP;
-    const float* kr = Ks + j * DP;
-    float a = 0.f;
-    for (int d = 0; d < D; ++d) a = fmaf(qr[d], kr[d], a);
-    Ps[p] = a * scale;
+    Ps[p] = attn_score(Qs + i * DP, Ks + j * DP, D, scale);
   }
   __syncthreads();
   for (int i = tid; i < nq; i += 256) {
@@ -712,100 +653,224 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ x, 
   }
 }
 
-inline int grid_for(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
+// ===========================================================================
+// Dispatch.  lin_check / linear_resolve and attn_small_resolve map what a call gives to the error the
+// entry returns or the kernel it launches (host arithmetic, no allocation: these calls run for
+// microseconds); the tables hold every instantiation; vggt_linear_f32_form and
+// vggt_attention_small_form expose the resolvers (tests/test_small_form.py pins them to the ladders
+// this code replaced).
+// ===========================================================================
+enum { L_WK = VGGT_LINEAR_FAMILY_WK, L_BLOCK = VGGT_LINEAR_FAMILY_BLOCK, L_SPLIT = VGGT_LINEAR_FAMILY_SPLIT };
+enum { A_MFMA = VGGT_ATTN_SMALL_FAMILY_MFMA, A_WG = VGGT_ATTN_SMALL_FAMILY_WG, A_WAVE = VGGT_ATTN_SMALL_FAMILY_WAVE };
+typedef vggt_linear_f32_form_t LinForm;
+typedef vggt_attention_small_form_t AttnForm;
+
+// What a linear call gives the dispatcher.  grouped: vggt_linear_f32_grouped (no gamma, no scratch)
+struct LinIn {
+  int M, N, K, act_in, epi, groups;
+  bool grouped, has_ptrs, has_gamma;
+  size_t ws_bytes;  // 0: no scratch
+};
+
+// The rules of the three linear entries, SHAPE before UNSUPPORTED
+int lin_check(const LinIn& in) {
+  if (in.M <= 0 || in.N <= 0 || in.K <= 0 || !in.has_ptrs) return VGGT_ERR_SHAPE;
+  if (in.grouped && (in.M > 256 || in.groups <= 0 || in.groups > 65535)) return VGGT_ERR_SHAPE;
+  if (!in.grouped && in.epi == VGGT_EPI_RESID_F32 && !in.has_gamma) return VGGT_ERR_SHAPE;
+  if ((in.act_in != 0 && in.act_in != 1) ||
+      (in.epi != VGGT_EPI_F32 && in.epi != VGGT_EPI_GELU_BF16 && in.epi != VGGT_EPI_RESID_F32))
+    return VGGT_ERR_UNSUPPORTED;
+  if (in.grouped && in.epi == VGGT_EPI_RESID_F32) return VGGT_ERR_UNSUPPORTED;  // the grouped entry takes no gamma
+  return VGGT_OK;
 }
 
-}  // namespace
-
-extern "C" int vggt_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M,
-                                  int N, int K, int act_in, int epi, float* out, int64_t ldo, const float* gamma,
-                                  void* ws, size_t ws_bytes, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return VGGT_ERR_SHAPE;
-  if (epi == VGGT_EPI_RESID_F32 && !gamma) return VGGT_ERR_SHAPE;
-  if ((act_in != 0 && act_in != 1) || (epi != VGGT_EPI_F32 && epi != VGGT_EPI_GELU_BF16 && epi != VGGT_EPI_RESID_F32))
-    return VGGT_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  if (M <= 256 && g_vggt_linear_wk > 0) {
-    linear_wk_dispatch(A, lda, W, ldw, bias, M, N, K, act_in, epi, out, ldo, gamma, s, 1, 0, 0, 0, 0);
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
+// The one place that picks a linear kernel (and reads the three linear knobs and the scratch size).
+LinForm linear_resolve(const LinIn& in) {
+  LinForm f{};
+  if ((f.rc = lin_check(in)) != VGGT_OK) return f;
+  const int M = in.M, N = in.N, K = in.K;
   const int gy = (M + 63) / 64;
+  f.mt = 4, f.splits = 1, f.kchunk = K, f.one_launch = 1;
+  if (in.grouped || (M <= 256 && g_vggt_linear_wk > 0)) {
+    // The in-workgroup split: each wave keeps ~g_vggt_linear_wk k (2..8 waves).  The wave count depends on K
+    // only, so a row's result does not depend on M (a grouped encode of three chunks gives each chunk's rows
+    // the bits of its own encode); 64-row slabs along blockIdx.y, groups along blockIdx.z.
+    const int wk = g_vggt_linear_wk > 0 ? g_vggt_linear_wk : 64;
+    f.family = L_WK;
+    f.mt = M <= 16 ? 1 : 4;
+    f.kw = 2;
+    while (f.kw < 8 && K > f.kw * wk) f.kw *= 2;
+    // k ranges of whole 64-k steps (the vector loop), the last wave takes the rest
+    f.kchunk = ((K + f.kw - 1) / f.kw + 63) / 64 * 64;
+    f.grid[0] = (N + 15) / 16, f.grid[1] = gy, f.grid[2] = in.grouped ? in.groups : 1;
+    f.threads = 64 * f.kw;
+    return f;
+  }
   const int blocks = ((N + 63) / 64) * gy;
   // split K until one block per CU is busy or a split would keep fewer than
   // g_vggt_linear_split_k k (skinny M: camera head, decoder)
   int splits = 1;
   while (splits < VGGT_LINEAR_F32_MAX_SPLITS && blocks * splits * 2 <= 512 && K / (splits * 2) >= g_vggt_linear_split_k)
     splits *= 2;
-  const int64_t mstride = (int64_t)gy * 64 * N;
-  // ws = [VGGT_LINEAR_F32_WS_COUNTERS zeroed tile words][partials]
+  // ws = [VGGT_LINEAR_F32_WS_COUNTERS zeroed tile words][partials of gy * 64 rows x N per split]
   const size_t cbytes = VGGT_LINEAR_F32_WS_COUNTERS * sizeof(unsigned);
-  while (splits > 1 && (!ws || ws_bytes < cbytes + (size_t)splits * mstride * sizeof(float))) splits /= 2;
-  const int kchunk = splits > 1 ? ((K + splits - 1) / splits + 15) / 16 * 16 : K;
-  float* part = splits > 1 ? (float*)((char*)ws + cbytes) : nullptr;
-  // one launch (last block per tile combines) while the tile words fit
-  unsigned* cnt =
-      (splits > 1 && blocks <= VGGT_LINEAR_F32_WS_COUNTERS && g_vggt_linear_one_launch) ? (unsigned*)ws : nullptr;
-  const dim3 grid((N + 63) / 64, gy, splits);
-#define LAUNCH(AI, E) \
-  linear_f32_kernel<AI, E><<<grid, 256, 0, s>>>(A, lda, W, ldw, bias, M, N, K, out, ldo, gamma, kchunk, part, cnt)
-  if (act_in == 0) {
-    if (epi == VGGT_EPI_F32) LAUNCH(0, VGGT_EPI_F32);
-    else if (epi == VGGT_EPI_GELU_BF16) LAUNCH(0, VGGT_EPI_GELU_BF16);
-    else LAUNCH(0, VGGT_EPI_RESID_F32);
+  const int64_t mstride = (int64_t)gy * 64 * N;
+  while (splits > 1 && in.ws_bytes < cbytes + (size_t)splits * mstride * sizeof(float)) splits /= 2;
+  f.family = splits > 1 ? L_SPLIT : L_BLOCK;
+  f.splits = splits;
+  if (splits > 1) f.kchunk = ((K + splits - 1) / splits + 15) / 16 * 16;
+  // one launch (last block per tile combines) while the tile words fit, else a reduce launch
+  f.one_launch = splits == 1 || (blocks <= VGGT_LINEAR_F32_WS_COUNTERS && g_vggt_linear_one_launch);
+  f.grid[0] = (N + 63) / 64, f.grid[1] = gy, f.grid[2] = splits;
+  f.threads = 256;
+  return f;
+}
+
+// Every instantiation, by index: epilogue e = epi - 1 (GELU, RESID, F32), KW = 2 << kwi, MT = 1 / 4
+typedef void (*LinWkFn)(const float*, int64_t, const float*, int64_t, const float*, int, int, int, float*, int64_t,
+                        const float*, int, int64_t, int64_t, int64_t, int64_t);
+typedef void (*LinBlockFn)(const float*, int64_t, const float*, int64_t, const float*, int, int, int, float*, int64_t,
+                           const float*, int, float*, unsigned*);
+typedef void (*LinReduceFn)(const float*, int, int64_t, int, int, const float*, float*, int64_t, const float*);
+template <typename Fn, int N>
+struct FnTable {
+  Fn at[N];
+};
+template <int... I>
+constexpr FnTable<LinWkFn, 36> lin_wk_table(std::integer_sequence<int, I...>) {
+  return {{linear_f32_wk_kernel<2 << (I / 2 % 3), (I % 2) ? 4 : 1, I / 18, I / 6 % 3 + 1>...}};
+}
+template <int... I>
+constexpr FnTable<LinBlockFn, 6> lin_block_table(std::integer_sequence<int, I...>) {
+  return {{linear_f32_kernel<I / 3, I % 3 + 1>...}};
+}
+template <int... I>
+constexpr FnTable<LinReduceFn, 3> lin_reduce_table(std::integer_sequence<int, I...>) {
+  return {{linear_f32_reduce<I + 1>...}};
+}
+constexpr auto kLinWk = lin_wk_table(std::make_integer_sequence<int, 36>{});        // [act][e][kwi][mt == 4]
+constexpr auto kLinBlock = lin_block_table(std::make_integer_sequence<int, 6>{});   // [act][e]
+constexpr auto kLinReduce = lin_reduce_table(std::make_integer_sequence<int, 3>{}); // [e]
+static_assert(VGGT_EPI_GELU_BF16 == 1 && VGGT_EPI_RESID_F32 == 2 && VGGT_EPI_F32 == 3, "the tables index epi - 1");
+
+struct LinArgs {
+  const float *A, *W, *bias, *gamma;
+  float* out;
+  int64_t lda, ldw, ldo, a_gs, w_gs, b_gs, o_gs;
+  void* ws;
+};
+
+int linear_run(const LinIn& in, const LinArgs& g, hipStream_t s) {
+  const LinForm f = linear_resolve(in);
+  if (f.rc != VGGT_OK) return f.rc;
+  const dim3 grid(f.grid[0], f.grid[1], f.grid[2]);
+  const int e = in.epi - 1;
+  if (f.family == L_WK) {
+    const int kwi = f.kw == 2 ? 0 : f.kw == 4 ? 1 : 2;
+    kLinWk.at[((in.act_in * 3 + e) * 3 + kwi) * 2 + (f.mt == 4)]<<<grid, f.threads, 0, s>>>(
+        g.A, g.lda, g.W, g.ldw, g.bias, in.M, in.N, in.K, g.out, g.ldo, g.gamma, f.kchunk, g.a_gs, g.w_gs, g.b_gs, g.o_gs);
   } else {
-    if (epi == VGGT_EPI_F32) LAUNCH(1, VGGT_EPI_F32);
-    else if (epi == VGGT_EPI_GELU_BF16) LAUNCH(1, VGGT_EPI_GELU_BF16);
-    else LAUNCH(1, VGGT_EPI_RESID_F32);
+    float* part = f.splits > 1 ? (float*)((char*)g.ws + VGGT_LINEAR_F32_WS_COUNTERS * sizeof(unsigned)) : nullptr;
+    unsigned* cnt = (f.splits > 1 && f.one_launch) ? (unsigned*)g.ws : nullptr;
+    kLinBlock.at[in.act_in * 3 + e]<<<grid, f.threads, 0, s>>>(g.A, g.lda, g.W, g.ldw, g.bias, in.M, in.N, in.K, g.out,
+                                                               g.ldo, g.gamma, f.kchunk, part, cnt);
+    if (part && !cnt) {
+      const int64_t total = (int64_t)in.M * in.N;
+      const int rg = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+      kLinReduce.at[e]<<<rg, 256, 0, s>>>(part, f.splits, (int64_t)f.grid[1] * 64 * in.N, in.M, in.N, g.bias, g.out,
+                                          g.ldo, g.gamma);
+    }
   }
-#undef LAUNCH
-  if (part && !cnt) {
-    const int64_t total = (int64_t)M * N;
-    const int rg = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (epi == VGGT_EPI_F32) linear_f32_reduce<VGGT_EPI_F32><<<rg, 256, 0, s>>>(part, splits, mstride, M, N, bias, out, ldo, gamma);
-    else if (epi == VGGT_EPI_GELU_BF16) linear_f32_reduce<VGGT_EPI_GELU_BF16><<<rg, 256, 0, s>>>(part, splits, mstride, M, N, bias, out, ldo, gamma);
-    else linear_f32_reduce<VGGT_EPI_RESID_F32><<<rg, 256, 0, s>>>(part, splits, mstride, M, N, bias, out, ldo, gamma);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+// What an attention call gives the dispatcher.  ptr_align: the largest power of two (bytes) that divides
+// all four base pointers
+struct AttnIn {
+  int dtype;  // with VGGT_ATTN_SMALL_EXACT
+  int batch, heads, nq, nk, D;
+  int64_t ldq, ldk, ldv, ldo;
+  int ptr_align;
+  bool has_ptrs;
+};
+
+// The one place that picks a small-window attention kernel (and reads the two environment switches).
+AttnForm attn_small_resolve(const AttnIn& in) {
+  AttnForm f{};
+  const int nq = in.nq, nk = in.nk, D = in.D;
+  if (in.batch <= 0 || in.heads <= 0 || nq <= 0 || nk <= 0 || nk > 128 || D <= 0 || D > 256 || !in.has_ptrs)
+    return f.rc = VGGT_ERR_SHAPE, f;
+  // the one-wave form, which takes whatever the other two do not: Ks[nk][D+1], Vs[nk][D+1], Qr[D]
+  const size_t lds_wave = (size_t)(2 * nk * (D + 1) + D) * sizeof(float);
+  if (lds_wave > 160 * 1024) return f.rc = VGGT_ERR_SHAPE, f;
+  const bool exact = (in.dtype & VGGT_ATTN_SMALL_EXACT) != 0;
+  const int dtype = in.dtype & ~VGGT_ATTN_SMALL_EXACT;
+  if (dtype != VGGT_DTYPE_BF16 && dtype != VGGT_DTYPE_F32) return f.rc = VGGT_ERR_UNSUPPORTED, f;
+  f.grid = in.batch * in.heads;
+  // the matrix-core form for bf16 windows of <= 16 x 16: four (batch, head) pairs per workgroup, 8-byte loads
+  if (g_vggt_small_knobs.attn_mfma && !exact && dtype == VGGT_DTYPE_BF16 && nq <= 16 && nk <= 16 && D % 16 == 0 &&
+      (in.ldq | in.ldk | in.ldv | in.ldo) % 4 == 0 && in.ptr_align % 8 == 0) {
+    f.family = A_MFMA;
+    f.dt = (D == 64 || D == 128) ? D : 0;
+    f.grid = (f.grid + 3) / 4;
+    f.threads = 256;
+    f.lds = 4 * 16 * D * 2;
+    return f;
   }
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+  // the workgroup form while Qs[nq][D+1], Ks[nk][D+1], Vs[nk][D], Ps[nq][nk] fit 64 KiB
+  const size_t lds_wg = ((size_t)(nq + nk) * (D + 1) + (size_t)nk * D + (size_t)nq * nk) * sizeof(float);
+  if (g_vggt_small_knobs.attn_wg && lds_wg <= 64 * 1024) {
+    f.family = A_WG;
+    f.threads = 256;
+    f.lds = (int)lds_wg;
+    return f;
+  }
+  f.family = A_WAVE;
+  f.threads = 64;
+  f.lds = (int)lds_wave;
+  return f;
 }
 
-extern "C" int vggt_linear_f32_grouped(const float* A, int64_t lda, int64_t a_gstride, const float* W, int64_t ldw,
-                                       int64_t w_gstride, const float* bias, int64_t b_gstride, int M, int N, int K,
-                                       int groups, int act_in, int epi, float* out, int64_t ldo, int64_t o_gstride,
-                                       void* stream) {
-  if (M <= 0 || M > 256 || N <= 0 || K <= 0 || groups <= 0 || groups > 65535) return VGGT_ERR_SHAPE;
-  if ((act_in != 0 && act_in != 1) || (epi != VGGT_EPI_F32 && epi != VGGT_EPI_GELU_BF16)) return VGGT_ERR_UNSUPPORTED;
-  linear_wk_dispatch(A, lda, W, ldw, bias, M, N, K, act_in, epi, out, ldo, nullptr, (hipStream_t)stream, groups,
-                     a_gstride, w_gstride, b_gstride, o_gstride);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+struct AttnArgs {
+  const void *q, *k, *v;
+  void* o;
+  int64_t qbs, kbs, obs;
+  float scale;
+};
+typedef void (*AttnStart)(const AttnForm&, const AttnIn&, const AttnArgs&, hipStream_t);
+template <typename T, auto KERNEL>
+void attn_start(const AttnForm& f, const AttnIn& in, const AttnArgs& g, hipStream_t s) {
+  KERNEL<<<f.grid, f.threads, f.lds, s>>>((const T*)g.q, in.ldq, g.qbs, (const T*)g.k, in.ldk, g.kbs, (const T*)g.v,
+                                          in.ldv, (T*)g.o, in.ldo, g.obs, in.heads, in.nq, in.nk, in.D, g.scale);
 }
-
-extern "C" int vggt_gated_update_prep(const float* memory, const float* update, int B, int Nt, int D, float* inp,
-                                      float* g_in, void* stream) {
-  if (B <= 0 || Nt <= 0 || D <= 0) return VGGT_ERR_SHAPE;
-  gated_update_prep_kernel<<<B * Nt, 256, 0, (hipStream_t)stream>>>(memory, update, Nt, D, inp, g_in);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+template <int DT>
+void attn_start_mfma(const AttnForm& f, const AttnIn& in, const AttnArgs& g, hipStream_t s) {
+  attn_small_mfma_kernel<DT><<<f.grid, f.threads, f.lds, s>>>(
+      (const bf16_t*)g.q, in.ldq, g.qbs, (const bf16_t*)g.k, in.ldk, g.kbs, (const bf16_t*)g.v, in.ldv, (bf16_t*)g.o,
+      in.ldo, g.obs, in.batch * in.heads, in.heads, in.nq, in.nk, in.D, g.scale);
 }
+// [family][dtype, or the matrix-core form's dt / 64]
+constexpr AttnStart kAttn[3][3] = {
+    {attn_start_mfma<0>, attn_start_mfma<64>, attn_start_mfma<128>},
+    {attn_start<float, attn_small_wg_kernel<float>>, attn_start<bf16_t, attn_small_wg_kernel<bf16_t>>, nullptr},
+    {attn_start<float, attn_small_kernel<float>>, attn_start<bf16_t, attn_small_kernel<bf16_t>>, nullptr}};
+static_assert(VGGT_DTYPE_F32 == 0 && VGGT_DTYPE_BF16 == 1, "kAttn indexes the dtype");
 
-extern "C" int vggt_gated_update_diff(const float* memory, const float* deltas, int rows, int D, float* g_in,
-                                      void* stream) {
-  if (rows <= 0 || D <= 0) return VGGT_ERR_SHAPE;
-  gated_update_diff_kernel<<<rows, 64, 0, (hipStream_t)stream>>>(memory, deltas, D, g_in);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
-}
+typedef void (*HeadnormFn)(float*, int64_t, int, int, int, const float*, const float*, float, const int32_t*, int,
+                           const float*, const float*, int);
+constexpr HeadnormFn kHeadnorm[3] = {headnorm_rope_f32_kernel<VGGT_ROPE_NONE>, headnorm_rope_f32_kernel<VGGT_ROPE_2D>,
+                                     headnorm_rope_f32_kernel<VGGT_ROPE_1D>};
+static_assert(VGGT_ROPE_NONE == 0 && VGGT_ROPE_2D == 1 && VGGT_ROPE_1D == 2, "kHeadnorm indexes the mode");
 
-extern "C" int vggt_gated_update_tail(const float* memory, const float* deltas, const float* logit, int rows, int D,
-                                      float* out, void* stream) {
-  if (rows <= 0 || D <= 0) return VGGT_ERR_SHAPE;
-  gated_update_tail_kernel<<<rows, 64, 0, (hipStream_t)stream>>>(memory, deltas, logit, D, out);
-  HIP_LAUNCH_CHECK();
-  return VGGT_OK;
+}  // namespace
+
+extern "C" int vggt_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M,
+                                  int N, int K, int act_in, int epi, float* out, int64_t ldo, const float* gamma,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  const LinIn in = {M, N, K, act_in, epi, 1, false, A && W && out, gamma != nullptr, ws ? ws_bytes : 0};
+  const LinArgs g = {A, W, bias, gamma, out, lda, ldw, ldo, 0, 0, 0, 0, ws};
+  return linear_run(in, g, (hipStream_t)stream);
 }
 
 extern "C" int vggt_linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M,
@@ -814,107 +879,97 @@ extern "C" int vggt_linear_f32(const float* A, int64_t lda, const float* W, int6
   return vggt_linear_f32_ws(A, lda, W, ldw, bias, M, N, K, act_in, epi, out, ldo, gamma, nullptr, 0, stream);
 }
 
+extern "C" int vggt_linear_f32_grouped(const float* A, int64_t lda, int64_t a_gstride, const float* W, int64_t ldw,
+                                       int64_t w_gstride, const float* bias, int64_t b_gstride, int M, int N, int K,
+                                       int groups, int act_in, int epi, float* out, int64_t ldo, int64_t o_gstride,
+                                       void* stream) {
+  const LinIn in = {M, N, K, act_in, epi, groups, true, A && W && out, false, 0};
+  const LinArgs g = {A, W, bias, nullptr, out, lda, ldw, ldo, a_gstride, w_gstride, b_gstride, o_gstride, nullptr};
+  return linear_run(in, g, (hipStream_t)stream);
+}
+
+extern "C" int vggt_linear_f32_form(int M, int N, int K, int act_in, int epi, int groups, int has_gamma,
+                                    size_t ws_bytes, vggt_linear_f32_form_t* form) {
+  const LinIn in = {M, N, K, act_in, epi, groups, groups != 0, true, has_gamma != 0, ws_bytes};
+  const LinForm f = linear_resolve(in);
+  if (form) *form = f;
+  return f.rc;
+}
+
+extern "C" int vggt_gated_update_prep(const float* memory, const float* update, int B, int Nt, int D, float* inp,
+                                      float* g_in, void* stream) {
+  if (B <= 0 || Nt <= 0 || D <= 0 || !memory || !update || !inp || !g_in) return VGGT_ERR_SHAPE;
+  gated_update_prep_kernel<<<B * Nt, 256, 0, (hipStream_t)stream>>>(memory, update, Nt, D, inp, g_in);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+extern "C" int vggt_gated_update_diff(const float* memory, const float* deltas, int rows, int D, float* g_in,
+                                      void* stream) {
+  if (rows <= 0 || D <= 0 || !memory || !deltas || !g_in) return VGGT_ERR_SHAPE;
+  gated_update_diff_kernel<<<rows, 64, 0, (hipStream_t)stream>>>(memory, deltas, D, g_in);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
+extern "C" int vggt_gated_update_tail(const float* memory, const float* deltas, const float* logit, int rows, int D,
+                                      float* out, void* stream) {
+  if (rows <= 0 || D <= 0 || !memory || !deltas || !logit || !out) return VGGT_ERR_SHAPE;
+  gated_update_tail_kernel<<<rows, 64, 0, (hipStream_t)stream>>>(memory, deltas, logit, D, out);
+  HIP_LAUNCH_CHECK();
+  return VGGT_OK;
+}
+
 extern "C" int vggt_attention_small(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk,
                                     int64_t k_bstride, const void* v, int64_t ldv, void* o, int64_t ldo,
                                     int64_t o_bstride, int dtype, int batch, int heads, int nq, int nk, int D,
                                     float scale, void* stream) {
-  if (batch <= 0 || heads <= 0 || nq <= 0 || nk <= 0 || nk > 128 || D <= 0 || D > 256) return VGGT_ERR_SHAPE;
-  const size_t lds = (size_t)(2 * nk * (D + 1) + D) * sizeof(float);
-  if (lds > 160 * 1024) return VGGT_ERR_SHAPE;
-  static bool attr_set = false;  // allow > 64 KiB dynamic LDS (gfx950: 160 KiB per workgroup)
-  if (!attr_set) {
+  const uintptr_t bits = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | 256;
+  const AttnIn in = {dtype, batch, heads, nq, nk, D, ldq, ldk, ldv, ldo, (int)(bits & -bits), q && k && v && o};
+  const AttnForm f = attn_small_resolve(in);
+  if (f.rc != VGGT_OK) return f.rc;
+  // once: the one-wave form may ask for > 64 KiB of dynamic LDS (gfx950: 160 KiB per workgroup)
+  static const bool attr = [] {
     (void)hipFuncSetAttribute((const void*)attn_small_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_small_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        160 * 1024);
-    attr_set = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // the matrix-core form for bf16 windows of <= 16 x 16 (VGGT_ATTN_SMALL_MFMA=0: the fp32 LDS form)
-  static const int use_mfma = getenv("VGGT_ATTN_SMALL_MFMA") ? atoi(getenv("VGGT_ATTN_SMALL_MFMA")) : 1;
-  const bool exact = (dtype & VGGT_ATTN_SMALL_EXACT) != 0;
-  dtype &= ~VGGT_ATTN_SMALL_EXACT;
-  if (use_mfma && !exact && dtype == VGGT_DTYPE_BF16 && nq <= 16 && nk <= 16 && D % 16 == 0 && D <= 256 &&
-      (ldq | ldk | ldv | ldo) % 4 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 7) == 0) {
-    const int pairs = batch * heads;
-    const int nwg = (pairs + 3) / 4;
-    const size_t lds_v = 4 * 16 * D * 2;
-#define VGGT_SMALL_MFMA(DT_)                                                                                       \
-  attn_small_mfma_kernel<DT_><<<nwg, 256, lds_v, s>>>((const bf16_t*)q, ldq, q_bstride, (const bf16_t*)k, ldk,       \
-                                                      k_bstride, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, o_bstride, \
-                                                      pairs, heads, nq, nk, D, scale)
-    if (D == 128) VGGT_SMALL_MFMA(128);
-    else if (D == 64) VGGT_SMALL_MFMA(64);
-    else VGGT_SMALL_MFMA(0);
-#undef VGGT_SMALL_MFMA
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  const int grid = batch * heads;
-  const size_t lds_wg = ((size_t)(nq + nk) * (D + 1) + (size_t)nk * D + (size_t)nq * nk) * sizeof(float);
-  static const int use_wg = getenv("VGGT_ATTN_SMALL_WG") ? atoi(getenv("VGGT_ATTN_SMALL_WG")) : 1;
-  if (use_wg && lds_wg <= 64 * 1024) {
-    if (dtype == VGGT_DTYPE_BF16)
-      attn_small_wg_kernel<bf16_t><<<grid, 256, lds_wg, s>>>((const bf16_t*)q, ldq, q_bstride, (const bf16_t*)k, ldk,
-                                                             k_bstride, (const bf16_t*)v, ldv, (bf16_t*)o, ldo,
-                                                             o_bstride, heads, nq, nk, D, scale);
-    else if (dtype == VGGT_DTYPE_F32)
-      attn_small_wg_kernel<float><<<grid, 256, lds_wg, s>>>((const float*)q, ldq, q_bstride, (const float*)k, ldk,
-                                                            k_bstride, (const float*)v, ldv, (float*)o, ldo, o_bstride,
-                                                            heads, nq, nk, D, scale);
-    else
-      return VGGT_ERR_UNSUPPORTED;
-    HIP_LAUNCH_CHECK();
-    return VGGT_OK;
-  }
-  if (dtype == VGGT_DTYPE_BF16)
-    attn_small_kernel<bf16_t><<<grid, 64, lds, s>>>((const bf16_t*)q, ldq, q_bstride, (const bf16_t*)k, ldk, k_bstride,
-                                                    (const bf16_t*)v, ldv, (bf16_t*)o, ldo, o_bstride, heads, nq, nk,
-                                                    D, scale);
-  else if (dtype == VGGT_DTYPE_F32)
-    attn_small_kernel<float><<<grid, 64, lds, s>>>((const float*)q, ldq, q_bstride, (const float*)k, ldk, k_bstride,
-                                                   (const float*)v, ldv, (float*)o, ldo, o_bstride, heads, nq, nk, D,
-                                                   scale);
-  else
-    return VGGT_ERR_UNSUPPORTED;
+    (void)hipFuncSetAttribute((const void*)attn_small_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return true;
+  }();
+  (void)attr;
+  const AttnArgs g = {q, k, v, o, q_bstride, k_bstride, o_bstride, scale};
+  kAttn[f.family][f.family == A_MFMA ? f.dt / 64 : dtype & ~VGGT_ATTN_SMALL_EXACT](f, in, g, (hipStream_t)stream);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
+}
+
+extern "C" int vggt_attention_small_form(int dtype, int nq, int nk, int D, int64_t ldq, int64_t ldk, int64_t ldv,
+                                         int64_t ldo, int ptr_align, int batch, int heads,
+                                         vggt_attention_small_form_t* form) {
+  const AttnIn in = {dtype, batch, heads, nq, nk, D, ldq, ldk, ldv, ldo, ptr_align, true};
+  const AttnForm f = attn_small_resolve(in);
+  if (form) *form = f;
+  return f.rc;
 }
 
 extern "C" int vggt_headnorm_rope_f32(float* buf, int64_t ld, int col_off, int M, int H, int D, const float* w,
                                       const float* b, float eps, int rope_mode, const int32_t* pos, int period,
                                       const float* cos_tab, const float* sin_tab, int tab_len, void* stream) {
   if (M <= 0) return M == 0 ? VGGT_OK : VGGT_ERR_SHAPE;
-  if (H <= 0 || D <= 0 || D > 1024 || (D % 4)) return VGGT_ERR_SHAPE;
+  if (H <= 0 || D <= 0 || D > 1024 || (D % 4) || !buf) return VGGT_ERR_SHAPE;
   if (rope_mode != VGGT_ROPE_NONE && (!pos || !cos_tab || !sin_tab || period <= 0 || tab_len <= 0))
     return VGGT_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = D * sizeof(float);
-  const int grid = M * H;
-  switch (rope_mode) {
-    case VGGT_ROPE_NONE:
-      headnorm_rope_f32_kernel<VGGT_ROPE_NONE><<<grid, 64, lds, s>>>(buf, ld, col_off, H, D, w, b, eps, pos, period,
-                                                                    cos_tab, sin_tab, tab_len);
-      break;
-    case VGGT_ROPE_2D:
-      headnorm_rope_f32_kernel<VGGT_ROPE_2D><<<grid, 64, lds, s>>>(buf, ld, col_off, H, D, w, b, eps, pos, period,
-                                                                  cos_tab, sin_tab, tab_len);
-      break;
-    case VGGT_ROPE_1D:
-      headnorm_rope_f32_kernel<VGGT_ROPE_1D><<<grid, 64, lds, s>>>(buf, ld, col_off, H, D, w, b, eps, pos, period,
-                                                                  cos_tab, sin_tab, tab_len);
-      break;
-    default: return VGGT_ERR_UNSUPPORTED;
-  }
+  if (rope_mode < 0 || rope_mode > VGGT_ROPE_1D) return VGGT_ERR_UNSUPPORTED;
+  kHeadnorm[rope_mode]<<<M * H, 64, D * sizeof(float), (hipStream_t)stream>>>(buf, ld, col_off, H, D, w, b, eps, pos,
+                                                                             period, cos_tab, sin_tab, tab_len);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }
 
 extern "C" int vggt_cast_f32_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int rows, int cols,
                                   void* stream) {
-  if (rows < 0 || cols % 4 || ldx % 4 || ldy % 4) return VGGT_ERR_SHAPE;
+  if (rows < 0 || cols % 4 || ldx % 4 || ldy % 4 || (rows > 0 && (!x || !y))) return VGGT_ERR_SHAPE;
   if (((uintptr_t)x % 16) || ((uintptr_t)y % 8)) return VGGT_ERR_ALIGN;
   if (rows == 0) return VGGT_OK;
-  cast_kernel<<<grid_for((int64_t)rows * cols / 4), 256, 0, (hipStream_t)stream>>>(x, ldx, (bf16_t*)y, ldy, rows, cols);
+  cast_kernel<<<grid_for((int64_t)rows * cols / 4, 8192), 256, 0, (hipStream_t)stream>>>(x, ldx, (bf16_t*)y, ldy, rows, cols);
   HIP_LAUNCH_CHECK();
   return VGGT_OK;
 }

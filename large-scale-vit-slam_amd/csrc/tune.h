@@ -23,6 +23,12 @@ struct GemmKnobs {
   int headnorm_tile;  // VGGT_HEADNORM_TILE (-1): the tile mode of vggt_gemm_headnorm while VGGT_TUNE_GEMM_TILE is auto
 };
 extern const GemmKnobs g_vggt_gemm_knobs;
+// The small-window attention dispatcher's environment-only switches (small.hip's attn_small_resolve; same terms)
+struct SmallKnobs {
+  int attn_mfma;  // VGGT_ATTN_SMALL_MFMA (1): 0 keeps bf16 windows of <= 16 x 16 off the matrix-core form
+  int attn_wg;    // VGGT_ATTN_SMALL_WG (1): 0 sends every window the matrix cores do not take to the one-wave form
+};
+extern const SmallKnobs g_vggt_small_knobs;
 // per-stream launch configuration (vggt_set_stream_config): the CUs a CU-masked
 // stream may use (0: the device's) and its VGGT_STREAM_* flags
 int vggt_stream_cu_count(void* stream);

@@ -4,7 +4,11 @@
 of 64).  Each kernel is timed with HIP events over R back-to-back launches on
 the current stream.  Used to iterate on single kernels between full bench runs.
 
-    python scripts/kbench.py [--reps 20] [--only gemm,norm,attn]   (train: not in the default set)
+    python scripts/kbench.py [--reps 20] [--only gemm,norm,attn]   (train, small: not in the default set)
+
+--only small: the latency-bound calls of small.hip at the shapes one chunk of bench.py's configuration
+(16 frames of 518 x 518, 1370 tokens per frame, 5 overlap frames, 8 memory tokens) issues; these run
+for microseconds, so the figure includes the host's launch cost (use --reps 200).
 """
 import argparse
 import json
@@ -149,6 +153,72 @@ def main():
         us = timeit(lambda: N.attention_small_bwd(q, k, v, do, gq, gkv[:, :C], gkv[:, C:], M // S, Ha, S, S, C // Ha, S,
                                                   S, S, S, S), args.reps)
         res["attention_small_bwd/16x16"] = {"us": round(us, 1), "gbs": round(M * C * 14 / us / 1e3, 1)}
+    if "small" in only:
+        f32 = lambda *sh: torch.randn(*sh, device=dev)  # noqa: E731
+        E = {"f32": N.EPI_F32, "gelu": N.EPI_GELU_BF16, "resid": N.EPI_RESID_F32}
+        # (name, M, N, K, epilogue, act_in): camera_head.py (dim 2048, 16 heads, M = 16 frames), alignment_head.py's
+        # decoder (dec 512, 8 heads: one chunk token against 16 frames + 8 memory tokens, 15 frame tokens against the
+        # chunk token; cross_attention.py forward_f32) and gated_update.py's gate MLP (8 memory tokens)
+        linears = [("cam_embed_pose", 16, 2048, 9, "f32", 0), ("cam_modulation", 16, 6144, 2048, "f32", 1),
+                   ("cam_qkv", 16, 6144, 2048, "f32", 0), ("cam_proj", 16, 2048, 2048, "resid", 0),
+                   ("cam_fc1", 16, 8192, 2048, "gelu", 0), ("cam_fc2", 16, 2048, 8192, "resid", 0),
+                   ("cam_pose_fc1", 16, 1024, 2048, "gelu", 0), ("cam_pose_fc2", 16, 9, 1024, "f32", 0),
+                   ("dec_project", 16, 512, 1024, "f32", 0), ("dec_frame_proj", 1, 4096, 512, "f32", 0),
+                   ("dec_chunk_q", 1, 512, 512, "f32", 0), ("dec_chunk_kv", 24, 1024, 512, "f32", 0),
+                   ("dec_chunk_fc1", 1, 2048, 512, "gelu", 0), ("dec_chunk_fc2", 1, 512, 2048, "resid", 0),
+                   ("dec_frame_q", 15, 512, 512, "f32", 0), ("dec_frame_fc1", 15, 2048, 512, "gelu", 0),
+                   ("dec_frame_fc2", 15, 512, 2048, "resid", 0), ("dec_se3_fc1", 15, 256, 512, "gelu", 0),
+                   ("dec_se3_fc2", 15, 7, 256, "f32", 0), ("gate_fc1", 8, 512, 1024, "gelu", 0),
+                   ("gate_fc2", 8, 1, 512, "f32", 0)]
+        for name, m, n, k, epi, act in linears:
+            a, w, bias, out, gam = f32(m, k), f32(n, k) * k ** -0.5, f32(n), f32(m, n), torch.rand(n, device=dev)
+            us = timeit(lambda: N.linear_f32(a, w, bias, out, E[epi], act_in=act, gamma=gam if epi == "resid" else None),
+                        args.reps)
+            res[f"linear_f32/{name}/{m}x{n}x{k}"] = {"us": round(us, 2), "form": N.linear_f32_form(m, n, k)["name"]}
+        # GatedUpdate (B = 1, Nt = 8, D = 512): its three stages and the grouped pair of the per-token delta MLPs
+        Nt, Dm = 8, 512
+        mem, upd, dl, logit = f32(1, Nt, Dm), f32(1, Dm), f32(1, Nt, Dm), f32(Nt)
+        inp, g_in, go = f32(1, Nt, 3 * Dm), f32(Nt, 2 * Dm), f32(1, Nt, Dm)
+        w1, b1, w2, b2, hid = f32(Nt, Dm, 3 * Dm) * 0.03, f32(Nt, Dm), f32(Nt, Dm, Dm) * 0.04, f32(Nt, Dm), f32(Nt, 1, Dm)
+        for name, fn in (("gated_update_prep", lambda: N.gated_update_prep(mem, upd, inp, g_in)),
+                         ("linear_f32_grouped/delta_fc1/8x1x512x1536",
+                          lambda: N.linear_f32_grouped(inp.transpose(0, 1), w1, b1, hid, N.EPI_GELU_BF16)),
+                         ("linear_f32_grouped/delta_fc2/8x1x512x512",
+                          lambda: N.linear_f32_grouped(hid, w2, b2, dl.transpose(0, 1), N.EPI_F32)),
+                         ("gated_update_diff", lambda: N.gated_update_diff(mem, dl, g_in)),
+                         ("gated_update_tail", lambda: N.gated_update_tail(mem, dl, logit, go))):
+            res[name] = {"us": round(timeit(fn, args.reps), 2)}
+        # temporal windows (cross_attention.py forward_rows_bf16: one group per token position, 16 frames against the
+        # 5 overlap frames or each other; 8 heads of 128, and of 64 at half the width), the decoder's and the
+        # camera trunk's fp32 windows
+        G = 1370
+        for nq, nk, Hh, Dh in ((16, 5, 8, 128), (16, 16, 8, 128), (16, 5, 8, 64), (16, 16, 8, 64)):
+            q, k, v = ((torch.randn(G * n, Hh * Dh, device=dev)).bfloat16() for n in (nq, nk, nk))
+            o = torch.empty_like(q)
+            us = timeit(lambda: N.attention_small(q, k, v, o, G, Hh, nq, nk, Dh, nq, nk, nq), max(3, args.reps // 4))
+            res[f"attention_small/bf16/{nq}x{nk}x{Dh}"] = {"us": round(us, 2), "form": N.attention_small_form(
+                N.DTYPE_BF16, nq, nk, Dh, batch=G, heads=Hh)["name"]}
+        for name, nq, nk, Hh, Dh in (("dec_chunk", 1, 24, 8, 64), ("dec_frame", 15, 1, 8, 64), ("cam_trunk", 16, 16, 16, 128)):
+            q, k, v = (f32(n, Hh * Dh) for n in (nq, nk, nk))
+            o = torch.empty_like(q)
+            us = timeit(lambda: N.attention_small(q, k, v, o, 1, Hh, nq, nk, Dh, nq, nk, nq), args.reps)
+            res[f"attention_small/f32/{name}/{nq}x{nk}x{Dh}"] = {"us": round(us, 2), "form": N.attention_small_form(
+                N.DTYPE_F32, nq, nk, Dh, heads=Hh)["name"]}
+        # the fp32 head norm: the decoder's q with RoPE 1D (15 rows, 8 heads of 64), the camera trunk's q of the packed qkv
+        pos = torch.arange(1, 16, dtype=torch.int32, device=dev)
+        cos, sin, hw, hb = f32(32, 64), f32(32, 64), torch.rand(64, device=dev), f32(64)
+        qd, qkv, cw, cb = f32(15, 512), f32(16, 6144), torch.rand(128, device=dev), f32(128)
+        for name, fn in (("headnorm_rope_f32/dec_q_rope1d/15x8x64",
+                          lambda: N.headnorm_rope_any(qd, 0, 8, 64, hw, hb, 1e-5, N.ROPE_1D, pos, 15, cos, sin)),
+                         ("headnorm_rope_f32/cam_q/16x16x128", lambda: N.headnorm_rope_any(qkv, 0, 16, 128, cw, cb, 1e-5))):
+            res[name] = {"us": round(timeit(fn, args.reps), 2)}
+        # the alignment head's input cast (16 x 1369 patch tokens of 2048)
+        xt = f32(16 * 1369, 2048)
+        yt = torch.empty(16 * 1369, 2048, device=dev, dtype=torch.bfloat16)
+        res["cast_f32_bf16/21904x2048"] = {"us": round(timeit(lambda: N.cast_f32_bf16(xt, yt), max(3, args.reps // 4)), 2)}
+        for key in [k for k in res if k.split("/")[0] in ("linear_f32", "linear_f32_grouped", "attention_small",
+                                                          "headnorm_rope_f32", "cast_f32_bf16") or k.startswith("gated_")]:
+            print(key, res[key], flush=True)
     if "attn" in only:
         qkv = (torch.randn(M, 3 * C, device=dev)).bfloat16()
         o = torch.empty(M, C, device=dev, dtype=torch.bfloat16)

@@ -2,8 +2,10 @@
 element or per row, against fp64: vggt_linear_f32 (three forms, and _grouped),
 vggt_attention_small (three kernels), vggt_headnorm_rope_f32 and the GatedUpdate prep / diff /
 tail kernels (the cast is in test_gpu_norm_edges.py).  Style, boxes and rules are those of
-test_gpu_train_edges.py (helpers in edge_rules.py); `_reach_*` restate the host dispatch, are
-asserted against the boundary shapes in test_reach_restated and printed with the figures.
+test_gpu_train_edges.py (helpers in edge_rules.py); the form each case is labelled with is the
+library's own answer (vggt_linear_f32_form, vggt_attention_small_form: `_lin_form`, `_attn_form`
+below; tests/test_small_form.py pins those answers to the dispatch as it stood), printed with
+the figures.
 
 Entry point, paths reached, rule:
   vggt_linear_f32
@@ -89,69 +91,24 @@ def N():
     return _native
 
 
-# ------------------------------------------------------------------ the dispatch, restated
-def _reach_linear(M, Nn, K, wk=64, split_k=128, ws=True):
-    if M <= 256 and wk > 0:
-        kw = 2
-        while kw < 8 and K > kw * wk:
-            kw *= 2
-        kchunk = -(-(-(-K // kw)) // 64) * 64
-        ranges = [(min(K, w * kchunk), min(K, min(K, w * kchunk) + kchunk)) for w in range(kw)]
-        return {"form": "in-workgroup split", "KW": kw, "MT": 1 if M <= 16 else 4, "slabs": -(-M // 64),
-                "kchunk": kchunk, "k_per_wave": [b - a for a, b in ranges]}
-    gy = -(-M // 64)
-    blocks = -(-Nn // 64) * gy
-    splits = 1
-    while splits < 32 and blocks * splits * 2 <= 512 and K // (splits * 2) >= split_k:
-        splits *= 2
-    if not (ws and M <= 256):
-        splits = 1
-    if splits == 1:
-        return {"form": "block, no split", "blocks": blocks}
-    kchunk = -(-(-(-K // splits)) // 16) * 16
-    return {"form": "cross-workgroup split", "splits": splits, "kchunk": kchunk,
-            "splits_past_K": [z for z in range(splits) if z * kchunk > K],
-            "waves_without_a_column": max(0, 4 - -(-(Nn - (-(-Nn // 64) - 1) * 64) // 16))}
+# ------------------------------------------------------------------ the dispatch, asked
+def _lin_form(N, M, Nn, K, **kw):
+    """What linear_f32 launches for this shape under the current knobs (the library's answer), with the
+    k ranges the form's kchunk gives."""
+    f = N.linear_f32_form(M, Nn, K, **kw)
+    r = {"form": f["name"], "grid": f["grid"], "threads": f["threads"], "kchunk": f["kchunk"]}
+    if f["name"] == "in-workgroup split":
+        beg = [min(K, w * f["kchunk"]) for w in range(f["kw"])]
+        r.update(KW=f["kw"], MT=f["mt"], slabs=f["grid"][1], k_per_wave=[min(K, b + f["kchunk"]) - b for b in beg])
+    elif f["name"] == "cross-workgroup split":
+        r.update(splits=f["splits"], one_launch=f["one_launch"],
+                 splits_past_K=[z for z in range(f["splits"]) if z * f["kchunk"] > K])
+    return r
 
 
-def _attn_lds_wg(nq, nk, D):
-    return ((nq + nk) * (D + 1) + nk * D + nq * nk) * 4
-
-
-def _attn_lds_wave(nk, D):
-    return (2 * nk * (D + 1) + D) * 4
-
-
-def _reach_attn(dt, nq, nk, D, use_mfma=True, use_wg=True):
-    """Box windows start 16-B aligned with row strides that are multiples of 8 elements, so the
-    matrix-core form's alignment conditions hold whenever its shape conditions do."""
-    if nk > 128 or D > 256 or _attn_lds_wave(nk, D) > 160 * 1024:
-        return "SHAPE"
-    if use_mfma and dt == BF and nq <= 16 and nk <= 16 and D % 16 == 0:
-        return "mfma"
-    if use_wg and _attn_lds_wg(nq, nk, D) <= 64 * 1024:
-        return "workgroup"
-    return "one-wave"
-
-
-def test_reach_restated():
-    r = _reach_linear(16, 17, 129)
-    assert r["KW"] == 4 and r["k_per_wave"] == [64, 64, 1, 0] and r["MT"] == 1
-    r = _reach_linear(256, 16, 520)
-    assert r["KW"] == 8 and r["kchunk"] == 128 and r["k_per_wave"] == [128] * 4 + [8, 0, 0, 0] and r["slabs"] == 4
-    assert [_reach_linear(1, 1, k)["KW"] for k in (1, 64, 65, 128, 129, 256, 260, 1000)] == [2, 2, 2, 2, 4, 4, 8, 8]
-    r = _reach_linear(16, 17, 520, wk=0, split_k=32)
-    assert r["splits"] == 16 and r["kchunk"] == 48 and r["splits_past_K"] == [11, 12, 13, 14, 15]
-    assert r["waves_without_a_column"] == 2
-    assert _reach_linear(257, 17, 260)["form"] == "block, no split" == _reach_linear(300, 65, 64, ws=False)["form"]
-    assert _reach_linear(17, 17, 65, wk=0)["form"] == "block, no split"
-    assert _attn_lds_wg(38, 38, 128) == 64448 and _attn_lds_wg(39, 39, 128) == 66300
-    assert _reach_attn(F32, 38, 38, 128) == "workgroup" and _reach_attn(F32, 39, 39, 128) == "one-wave"
-    assert _attn_lds_wave(79, 256) == 163448 and _reach_attn(F32, 2, 79, 256) == "one-wave"
-    assert _reach_attn(F32, 2, 80, 256) == "SHAPE" == _reach_attn(BF, 1, 129, 16)
-    assert _reach_attn(BF, 16, 16, 64) == "mfma" and _reach_attn(BF, 17, 16, 64) == "workgroup"
-    assert _reach_attn(BF, 16, 17, 64) == "workgroup" == _reach_attn(BF, 4, 4, 24)
-    assert [_reach_attn(F32, 3, nk, D) for nk, D in ((128, 68), (64, 200), (65, 200))] == ["one-wave"] * 3
+def _attn_form(N, dt, nq, nk, D, B=1, H=1, **kw):
+    """What attention_small launches for this window in this process (the library's answer)."""
+    return N.attention_small_form(N.DTYPE_BF16 if dt == BF else N.DTYPE_F32, nq, nk, D, batch=B, heads=H, **kw)
 
 
 # ================================================================== 9. linear_f32
@@ -251,7 +208,7 @@ def test_linear_f32_in_workgroup_split(N, K):
                     tag = f"linear_f32 wk M={M} N={Nn} K={K} epi={epi} act={act}"
                     worst = max(worst, _lin_check(errs, tag, rn, epi, act, _lin_run(N, rn, epi, act), False, K))
     print(f"interval linear_f32 in-workgroup K={K}: worst ratio {worst:.3f}")
-    _done(errs, *[("linear_f32", M, 17, K, _reach_linear(M, 17, K)) for M in (16, 17, 256)])
+    _done(errs, *[("linear_f32", M, 17, K, _lin_form(N, M, 17, K)) for M in (16, 17, 256)])
 
 
 XWG = [(M, Nn, K) for K in (64, 65, 129, 520, 1000) for M in (1, 16, 17, 65) for Nn in (1, 17, 65)]
@@ -264,7 +221,8 @@ def test_linear_f32_cross_workgroup_split(N, split_k):
     counters zero afterwards."""
     errs, worst, forms = [], 0.0, {}
     for M, Nn, K in XWG:
-        r = _reach_linear(M, Nn, K, wk=0, split_k=split_k)
+        with _Tune(N, wk=0, split_k=split_k):
+            r = _lin_form(N, M, Nn, K)
         forms[r["form"]] = forms.get(r["form"], 0) + 1
         ex, rn = _lin_host(M, Nn, K, True), _lin_host(M, Nn, K, False)
         for epi in (EPI_F32, EPI_GELU, EPI_RESID):
@@ -285,7 +243,8 @@ def test_linear_f32_cross_workgroup_split(N, split_k):
     if bool((_bits(cnt) != 0).any()):
         errs.append("tile counters not left zero")
     print(f"interval linear_f32 cross-workgroup split_k={split_k}: worst ratio {worst:.3f}; forms {forms}")
-    _done(errs, ("linear_f32", 16, 17, 520, _reach_linear(16, 17, 520, wk=0, split_k=split_k)))
+    with _Tune(N, wk=0, split_k=split_k):
+        _done(errs, ("linear_f32", 16, 17, 520, _lin_form(N, 16, 17, 520)))
 
 
 @pytest.mark.parametrize("M,wk", [(257, None), (300, None), (1, 0), (17, 0), (64, 0), (65, 0)])
@@ -293,10 +252,10 @@ def test_linear_f32_block_form_without_split(N, M, wk):
     errs, worst = [], 0.0
     for K in (9, 64, 65, 260) if wk is None else (9, 64, 65):
         for Nn in (1, 17, 65):
-            r = _reach_linear(M, Nn, K, wk=64 if wk is None else 0)
-            assert r["form"] == "block, no split", r
             ex, rn = _lin_host(M, Nn, K, True), _lin_host(M, Nn, K, False)
             with _Tune(N, wk=wk):
+                r = _lin_form(N, M, Nn, K)
+                assert r["form"] == "block, no split", r
                 for epi in (EPI_F32, EPI_RESID):
                     _lin_check(errs, f"linear_f32 block exact M={M} N={Nn} K={K} epi={epi}", ex, epi, 0,
                                _lin_run(N, ex, epi, 0), True, K)
@@ -305,7 +264,8 @@ def test_linear_f32_block_form_without_split(N, M, wk):
                         tag = f"linear_f32 block M={M} N={Nn} K={K} epi={epi} act={act}"
                         worst = max(worst, _lin_check(errs, tag, rn, epi, act, _lin_run(N, rn, epi, act), False, K))
     print(f"interval linear_f32 block M={M}: worst ratio {worst:.3f}")
-    _done(errs, ("linear_f32", M, _reach_linear(M, 17, 260, wk=64 if wk is None else 0)))
+    with _Tune(N, wk=wk):
+        _done(errs, ("linear_f32", M, _lin_form(N, M, 17, 260)))
 
 
 def test_linear_f32_silu_alone(N):
@@ -404,10 +364,9 @@ def _attn_host(q, k, v, scale, form, calc):
     return o.permute(0, 2, 1, 3)
 
 
-def _attn_case(N, errs, dt, B, H, nq, nk, D, kind="random", scale=None, use_mfma=True, use_wg=True):
+def _attn_case(N, errs, dt, B, H, nq, nk, D, kind="random", scale=None):
     g = _gen(30, dt == BF, B, H, nq, nk, D, len(kind))
     q, k, v = _attn_inputs(dt, B, H, nq, nk, D, kind, g)
-    form = _reach_attn(dt, nq, nk, D, use_mfma, use_wg)
     sc = D ** -0.5 if scale is None else scale
     qbs, kbs, obs = nq + 2, nk + 1, nq + 3
 
@@ -418,6 +377,9 @@ def _attn_case(N, errs, dt, B, H, nq, nk, D, kind="random", scale=None, use_mfma
 
     qb, kb, vb = rows(q, nq, qbs, NAN), rows(k, nk, kbs, NAN), rows(v, nk, kbs, NAN)
     ob = Box(torch.full((B * obs, H * D), SENT, dtype=dt), SENT, cols=(16, 8))
+    views = (qb.v, kb.v, vb.v, ob.v)
+    align = min(16, *(t.data_ptr() & -t.data_ptr() for t in views))
+    form = _attn_form(N, dt, nq, nk, D, B, H, ptr_align=align, **{"ld" + n: t.stride(0) for n, t in zip("qkvo", views)})["name"]
     N.attention_small(qb.v, kb.v, vb.v, ob.v, B, H, nq, nk, D, qbs, kbs, obs, scale=sc)
     full = ob.got().reshape(B, obs, H, D)
     got = full[:, :nq]
@@ -450,7 +412,7 @@ def test_attention_small_mfma(N, D):
 def test_attention_small_workgroup(N, dt):
     errs, forms = [], []
     for nq, nk, D in SMALL_LIST + [(38, 38, 128)]:
-        forms.append(((nq, nk, D), _attn_case(N, errs, dt, 2, 3, nq, nk, D), _attn_lds_wg(nq, nk, D)))
+        forms.append(((nq, nk, D), _attn_case(N, errs, dt, 2, 3, nq, nk, D), _attn_form(N, dt, nq, nk, D, 2, 3)["lds"]))
     for kind, sc in (("peaked", None), ("equal", None), ("random", 0.3)):
         _attn_case(N, errs, dt, 3, 2, 17, 7, 64, kind, sc)
     assert all(f == ("mfma" if dt == BF and nq <= 16 and nk <= 16 and D % 16 == 0 else "workgroup")
@@ -463,7 +425,7 @@ def test_attention_small_one_wave(N, dt):
     errs, forms = [], []
     for nq, nk, D in [(39, 39, 128), (3, 128, 68), (3, 64, 200), (3, 65, 200), (2, 79, 256)]:
         f = _attn_case(N, errs, dt, 2, 1 if D == 256 else 2, nq, nk, D)
-        forms.append(((nq, nk, D), f, _attn_lds_wave(nk, D)))
+        forms.append(((nq, nk, D), f, _attn_form(N, dt, nq, nk, D)["lds"]))
         assert f == "one-wave"
     for kind, sc in (("peaked", None), ("equal", None), ("random", 0.3)):
         _attn_case(N, errs, dt, 2, 2, 3, 128, 68, kind, sc)
@@ -472,31 +434,31 @@ def test_attention_small_one_wave(N, dt):
 
 def test_attention_small_shape_errors(N):
     for nq, nk, D in ((2, 80, 256), (1, 129, 16)):
-        assert _reach_attn(F32, nq, nk, D) == "SHAPE"
+        assert _attn_form(N, F32, nq, nk, D)["rc"] == ERR_SHAPE
         t = torch.zeros(nk + nq, D, device="cuda")
         _raises(ERR_SHAPE, N.attention_small, t, t, t, t, 1, 1, nq, nk, D, nq, nk, nq)
     torch.cuda.synchronize()
 
 
-def _attn_small_sweep(N, use_mfma, use_wg):
+def _attn_small_sweep(N):
     """The small list on the forms the two environment switches leave (a child process)."""
     out = {}
     for dt in (F32, BF):
         for nq, nk, D in SMALL_LIST:
             errs = []
-            form = _attn_case(N, errs, dt, 2, 3, nq, nk, D, use_mfma=use_mfma, use_wg=use_wg)
+            form = _attn_case(N, errs, dt, 2, 3, nq, nk, D)
             out[f"{_dtn(dt)},{nq},{nk},{D}"] = {"form": form, "errs": errs}
     figs = {str(k): v for k, v in FIG.items()}
     return out, figs
 
 
 _CHILD = """
-import json, os
+import json
 import torch
 from aligned_vggt import _native as N
 import test_gpu_small_edges as T
 N.lib()
-res, figs = T._attn_small_sweep(N, os.environ.get("VGGT_ATTN_SMALL_MFMA") != "0", os.environ.get("VGGT_ATTN_SMALL_WG") != "0")
+res, figs = T._attn_small_sweep(N)
 torch.cuda.synchronize()
 print(json.dumps({"cases": res, "figs": figs}))
 """
@@ -657,6 +619,113 @@ def test_gated_update_tail(N, degenerate):
         if not _guards_ok(obuf, out.numel()):
             errs.append(tag + ": guards overwritten")
     _done(errs)
+
+
+# ================================================================== 13. NULL pointers, first calls from two threads
+# Each case sets one required pointer of an otherwise valid call to NULL: VGGT_ERR_SHAPE, and the
+# buffers behind every other pointer (guards included) keep their bits -- nothing was launched.
+NULL_ARGS = {
+    "vggt_linear_f32": "A lda W ldw bias M N K act epi out ldo gamma",
+    "vggt_linear_f32_ws": "A lda W ldw bias M N K act epi out ldo gamma ws ws_bytes",
+    "vggt_linear_f32_grouped": "A lda a_gs W ldw w_gs bias b_gs M N K groups act epi out ldo o_gs",
+    "vggt_attention_small": "q ldq qbs k ldk kbs v ldv o ldo obs dtype batch heads nq nk D scale",
+    "vggt_headnorm_rope_f32": "buf ld col_off Mh H Dh w b eps mode pos period cos sin tab",
+    "vggt_gated_update_prep": "memory update B Nt Dg inp g_in",
+    "vggt_gated_update_diff": "memory deltas rows Dg g_in",
+    "vggt_gated_update_tail": "memory deltas logit rows Dg tail_out",
+    "vggt_cast_f32_bf16": "x ldx y ldy crows ccols",
+}
+NULL_RULES = {
+    "vggt_linear_f32": ("A", "W", "out", "gamma"),
+    "vggt_linear_f32_ws": ("A", "W", "out", "gamma"),
+    "vggt_linear_f32_grouped": ("A", "W", "out"),
+    "vggt_attention_small": ("q", "k", "v", "o"),
+    "vggt_headnorm_rope_f32": ("buf",),
+    "vggt_gated_update_prep": ("memory", "update", "inp", "g_in"),
+    "vggt_gated_update_diff": ("memory", "deltas", "g_in"),
+    "vggt_gated_update_tail": ("memory", "deltas", "logit", "tail_out"),
+    "vggt_cast_f32_bf16": ("x", "y"),
+}
+
+
+def test_null_pointers_are_shape_errors(N):
+    L, st = N.lib(), N._stream()
+    g = _gen(60)
+    shapes = {"A": (3, 8), "W": (17, 8), "bias": (1, 17), "out": (3, 24), "gamma": (1, 17), "ws": (1, 4096),
+              "q": (2, 16), "k": (2, 16), "v": (2, 16), "o": (2, 16), "buf": (3, 8), "w": (1, 4), "b": (1, 4),
+              "memory": (2, 4), "update": (1, 4), "deltas": (2, 4), "logit": (1, 2), "inp": (2, 12), "g_in": (2, 8),
+              "tail_out": (2, 4), "x": (3, 8)}
+    bufs = {k: Box(torch.randn(*sh, generator=g), SENT) for k, sh in shapes.items()}
+    bufs["y"] = Box(torch.randn(3, 8, generator=g).to(BF), SENT)
+    addr = {k: b.v.data_ptr() for k, b in bufs.items()}
+    ld = {k: b.v.stride(0) for k, b in bufs.items()}
+    # M = 3, N = 17, K = 5; nq = nk = 2, D = 16; head norm D = 4, H = 1, M = 3; GatedUpdate rows = 2, D = 4
+    base = dict(addr, lda=ld["A"], ldw=ld["W"], ldo=ld["out"], M=3, N=17, K=5, act=0, epi=EPI_RESID, ws_bytes=4096 * 4,
+                a_gs=0, w_gs=0, b_gs=0, o_gs=0, groups=1, ldq=ld["q"], ldk=ld["k"], ldv=ld["v"], qbs=2, kbs=2, obs=2,
+                dtype=N.DTYPE_F32, batch=1, heads=1, nq=2, nk=2, D=16, scale=0.25, ld=ld["buf"], col_off=0,
+                Mh=3, H=1, Dh=4, eps=EPS, mode=0, pos=None, period=1, cos=None, sin=None, tab=0, B=1, Nt=2,
+                Dg=4, rows=2, ldx=ld["x"], ldy=ld["y"], crows=3, ccols=8)
+    bad = []
+    for entry, names in NULL_ARGS.items():
+        args = dict(base, epi=EPI_F32) if entry == "vggt_linear_f32_grouped" else dict(base)
+        if entry == "vggt_attention_small":
+            args["ldo"] = ld["o"]
+        for null in NULL_RULES[entry]:
+            rc = getattr(L, entry)(*[None if k == null else args[k] for k in names.split()], st)
+            if rc != ERR_SHAPE:
+                bad.append(f"{entry} with {null} NULL: returned {rc}, want {ERR_SHAPE}")
+    torch.cuda.synchronize()
+    for k, b in bufs.items():
+        if not torch.equal(_bits(b.dev.cpu()), _bits(b.host)):
+            bad.append(f"buffer {k} was written by a refused call")
+    assert not bad, "\n".join(bad)
+
+
+_TWO_THREADS = """
+import hashlib, json, threading
+import torch
+from aligned_vggt import _native as N
+import edge_rules as R
+N.lib()
+nq, nk, D = 2, 79, 256
+assert N.attention_small_form(N.DTYPE_F32, nq, nk, D)["name"] == "one-wave" and N.attention_small_form(N.DTYPE_F32, nq, nk, D)["lds"] > 65536
+g = R._gen(61)
+q, k, v = (torch.randn(n, D, generator=g).cuda() for n in (nq, nk, nk))
+outs = [torch.full((nq + 2, D), R.SENT, device="cuda") for _ in range(3)]
+streams = [torch.cuda.Stream() for _ in range(2)]
+torch.cuda.synchronize()
+gate, errs = threading.Barrier(2), []
+def first_call(i):
+    try:
+        with torch.cuda.stream(streams[i]):
+            gate.wait()
+            N.attention_small(q, k, v, outs[i][1:1 + nq], 1, 1, nq, nk, D, nq, nk, nq)
+    except Exception as e:
+        errs.append(repr(e))
+ts = [threading.Thread(target=first_call, args=(i,)) for i in range(2)]
+[t.start() for t in ts]
+[t.join() for t in ts]
+torch.cuda.synchronize()
+N.attention_small(q, k, v, outs[2][1:1 + nq], 1, 1, nq, nk, D, nq, nk, nq)
+torch.cuda.synchronize()
+print(json.dumps({"errs": errs, "sha": [hashlib.sha256(R._bits(o.cpu()).numpy().tobytes()).hexdigest() for o in outs],
+                  "finite": bool(torch.isfinite(outs[2]).all()), "guards": bool((outs[2][0] == R.SENT).all() and (outs[2][-1] == R.SENT).all())}))
+"""
+
+
+def test_attention_small_first_calls_from_two_threads(N):
+    """The one-wave form at (2, 79, 256) needs 163,448 B of dynamic LDS, which the kernel may only ask for
+    once its attribute is set; the entry sets it on its first call.  Two host threads make the first two
+    calls of a fresh process at once (on a stream each): both outputs, guard rows included, are the bits of
+    a third, single-threaded call."""
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join(p for p in sys.path if p))
+    r = subprocess.run([sys.executable, "-c", _TWO_THREADS], env=env, capture_output=True, text=True, timeout=300,
+                       cwd=os.path.dirname(os.path.abspath(__file__)))
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert not got["errs"], got["errs"]
+    assert got["finite"] and got["guards"]
+    assert got["sha"][0] == got["sha"][2] == got["sha"][1], got["sha"]
 
 
 def test_figures_small():
