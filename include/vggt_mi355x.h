@@ -1257,6 +1257,85 @@ size_t vggt_depth_scale_ws_bytes(int B, int64_t n);
 int vggt_depth_scale_l1(const float* pred, const float* conf, const float* gt, const void* mask, int B, int64_t n,
                         int64_t bstride, float* scale_out, void* state_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ======================================================================
+ * GT alignment sim3_from_points (csrc/gt_points.hip): the reference's
+ * umeyama_alignment_from_points (utils/alignment.py:372-426) and umeyama
+ * (:6-59) on the device: percentile threshold, selection, compaction and the
+ * closed-form Sim(3), with no host visit.
+ *
+ * Per batch element b, over the first P = W H Wimg pixels of that element
+ * (W = min(seq_width, S)): pred and gt are points (P, 3) fp32, conf is (P,)
+ * fp32, mask is (P,) one byte per pixel.  Element b of each tensor starts
+ * b * its own batch stride after the pointer, counted in that tensor's
+ * elements (floats for pred, conf and gt; bytes for the mask): the call is
+ * [:, :seq_width] of (B, S, ...) tensors, so conf_bs and mask_bs are
+ * S H Wimg >= P and pred_bs and gt_bs are 3 S H Wimg >= 3 P.  The four
+ * strides are independent and ignored when B == 1.
+ *
+ * Threshold: thr = np.percentile(conf, q), method "linear", as numpy
+ * computes it for a float32 array and a Python-float q: every operation
+ * rounded to fp32 on its own, no fused multiply-add:
+ *     h  = (float)(P - 1) * ((float)q / 100.0f)
+ *     lo = min((int64)floorf(h), P - 1)
+ *     g  = h - floorf(h)
+ *     hi = min(lo + 1, P - 1)
+ *     a  = v[lo];  c = v[hi]        order statistics, 0-based, in
+ *                                   vggt_kth_value_f32's order
+ *     d  = c - a
+ *     thr = a + d * g;  if (g >= 0.5f) thr = c - d * (1.0f - g)
+ *   (lo is clamped because h can round above P - 1 once P > 2^24; numpy
+ *   takes the last element there.)  If any conf of the prefix is NaN, thr is
+ *   NaN, as numpy's.  The select compares -0 and +0 equal and reports a
+ *   selected zero as +0; no comparison against thr can tell the difference.
+ * Selection: a pixel is kept when mask > 0 && conf >= thr && conf > 1e-5f;
+ *   n counts the kept pixels; X and Y are the kept pred and gt rows in
+ *   row-major (S, H, W) order, the order of boolean indexing.
+ * Columns: VGGT_GT_POINTS_REFERENCE: sample i is x_i = (Xf[i], Xf[n + i],
+ *   Xf[2n + i]) with Xf = X.reshape(-1), and Y alike: the reference's
+ *   reshape(3, -1) of an (n, 3) selection, sic.  VGGT_GT_POINTS_POINTS:
+ *   x_i = X[i], the per-point fit that the reference's docstring describes.
+ * Umeyama: the means, sigma_x = E|x - mx|^2 and the centred cross-covariance
+ *   E[(y - my)(x - mx)^T] in fp64 from the fp32 values, in two passes:
+ *   per-lane partials, then one record per workgroup, added in a fixed order
+ *   that depends on n alone (no floating-point atomics); R = U diag(1, 1, d)
+ *   V^T and c = tr(D diag(1, 1, d)) / sigma_x from the library's 3x3 SVD;
+ *   t = my - c R mx; R, t and c rounded to fp32 once.
+ *
+ * T: B x 16 floats, row-major 4x4 [R t; 0 0 0 1].  scale: B floats (c).
+ * state: B records of VGGT_GT_POINTS_STATE_BYTES, 8-byte aligned: int64 n;
+ * int64 count of NaN confidences; float thr; float a; float c; 4 bytes of
+ * padding.  n == 0 (which a NaN thr implies): NaN in T[:3] and in scale; the
+ * host route raises inside LAPACK there.  n == 1: sigma_x == 0, so scale and
+ * t are NaN (0 / 0), as the reference's 1 / sigma_x makes them.  pred and gt
+ * of an unselected pixel are never read: a NaN or inf there reaches no sum.
+ * The result is a function of the inputs alone: bitwise repeatable, and an
+ * element's result does not depend on the rest of the batch.  No host
+ * synchronisation.
+ *
+ * Geometry: one 256-lane workgroup takes VGGT_GT_POINTS_GROUP consecutive
+ * pixels of one element (in the two sum passes: samples), so a pass launches
+ * ceil(P / VGGT_GT_POINTS_GROUP) x B workgroups; there is no grid cap and no
+ * workgroup makes a second trip.  The confidences of the threshold passes
+ * are read 128 bits per lane when conf is 16-byte aligned (and conf_bs % 4
+ * == 0 when B > 1), element by element otherwise.
+ *
+ * ws: 16-byte aligned, >= vggt_gt_points_align_ws_bytes(B, P) (about
+ * 24.2 B P bytes: the compacted rows have room for n = P; 0 for a shape the
+ * call refuses).  VGGT_ERR_SHAPE: B < 1, B > 65535, P < 1, P >= 2^31 - 256,
+ * with B > 1 a stride below P (pred_bs, gt_bs: below 3 P), q outside
+ * [0, 100] or NaN, a null pointer, a misaligned or short ws.  Then
+ * VGGT_ERR_UNSUPPORTED: columns not one of the two.  Then VGGT_ERR_ALIGN:
+ * pred, conf, gt, T or scale not 4-byte aligned, state not 8-byte aligned.
+ * ====================================================================== */
+#define VGGT_GT_POINTS_REFERENCE 0
+#define VGGT_GT_POINTS_POINTS 1
+#define VGGT_GT_POINTS_STATE_BYTES 32
+#define VGGT_GT_POINTS_GROUP 4096
+size_t vggt_gt_points_align_ws_bytes(int B, int64_t P);
+int vggt_gt_points_align(const float* pred, int64_t pred_bs, const float* conf, int64_t conf_bs, const float* gt,
+                         int64_t gt_bs, const void* mask, int64_t mask_bs, int B, int64_t P, float q, int columns,
+                         float* T, float* scale, void* state, void* ws, size_t ws_bytes, void* stream);
+
 /* MFMA peak probe (diagnostic; BASELINE.md §2 asks for a measured MFMA microbenchmark with its clock):
  * nwg workgroups of 4 waves issue iters x 8 v_mfma_f32_32x32x16_bf16 each on the bf16 operands
  * (nwg * 256 * 16 elements: random or zeros), 32768 FLOP per MFMA; stamps[4 * wg] = s_memtime before /

@@ -133,6 +133,9 @@ _SIGS = {
     "vggt_depth_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     # GT scale alignment (csrc/gt_align.hip)
     "vggt_depth_scale_l1": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    # GT alignment from points (csrc/gt_points.hip)
+    "vggt_gt_points_align": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _f, _i, _vp, _vp, _vp, _vp,
+                             ctypes.c_size_t, _vp],
     # GT alignment from poses and the trajectory-metric terms (csrc/pose.hip)
     "vggt_gt_pose_align": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "vggt_trajectory_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -142,7 +145,7 @@ _WS_FNS = {"vggt_colred_workspace_bytes": [_i, _i], "vggt_layernorm_bwd_workspac
            "vggt_wgrad_bf16_workspace_bytes": [_i, _i, _i], "vggt_attention_ws_bytes": [_i, _i, _i, _i, _i, _vp],
            "vggt_nn1_workspace_bytes": [_i, _i64, _i64], "vggt_kth_value_ws_bytes": [_i64],
            "vggt_prepare_clouds_ws_bytes": [_i, _i, _i, _i, _i], "vggt_depth_loss_ws_bytes": [_i, _i, _i, _i],
-           "vggt_depth_scale_ws_bytes": [_i, _i64]}
+           "vggt_depth_scale_ws_bytes": [_i, _i64], "vggt_gt_points_align_ws_bytes": [_i, _i64]}
 
 _lib = None
 
@@ -1411,6 +1414,73 @@ def depth_scale_state(state: torch.Tensor) -> list:
         i = row[4:6].view(torch.int32)
         out.append({"cnt": int(row[0]), "total": int(row[1]), "below": int(row[2]), "through": int(row[3]),
                     "mean": float(f[0]), "e": int(i[1]), "key": int(i[2]) & 0xffffffff, "wmax": float(f[3])})
+    return out
+
+
+# ---------------------------------------------------------------- GT alignment from points (csrc/gt_points.hip)
+GT_POINTS_REFERENCE, GT_POINTS_POINTS = 0, 1
+GT_POINTS_STATE_WORDS = 4  # VGGT_GT_POINTS_STATE_BYTES / 8
+GT_POINTS_GROUP = 4096     # VGGT_GT_POINTS_GROUP: pixels of one workgroup
+
+
+def gt_points_align_ws_bytes(B: int, P: int) -> int:
+    """vggt_gt_points_align_ws_bytes (host arithmetic only)."""
+    return int(lib().vggt_gt_points_align_ws_bytes(int(B), int(P)))
+
+
+def _batch_block(t: torch.Tensor, inner: int, name: str) -> int:
+    """The batch stride of a (B, ...) tensor whose per-batch blocks are contiguous
+    (``[:, :seq_width]`` of a contiguous tensor is one); raises otherwise."""
+    if not t[0].is_contiguous() or t[0].numel() != inner:
+        raise RuntimeError(f"{name}: contiguous per-batch blocks of {inner} elements expected, got shape "
+                           f"{tuple(t.shape)} with strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else inner
+
+
+def gt_points_align(pred: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, q: float,
+                    columns: int = GT_POINTS_REFERENCE):
+    """vggt_gt_points_align on the current stream: pred and gt (B, ..., 3) fp32 points, conf
+    (B, ...) fp32 and a bool or uint8 mask (B, ...), P pixels per batch element, on one device,
+    each with contiguous per-batch blocks (a batch stride larger than the block is allowed) ->
+    (T (B, 4, 4) fp32, scale (B,) fp32, state (B, GT_POINTS_STATE_WORDS) int64: see
+    gt_points_state).  Nothing visits the host."""
+    B = pred.shape[0]
+    P = conf[0].numel()
+    for t in (pred, conf, gt, mask):
+        _dev(t, "gt_points_align")
+        if t.device != pred.device or t.shape[0] != B:
+            raise RuntimeError("gt_points_align: four tensors of one batch size on one device")
+    if not (pred.dtype == conf.dtype == gt.dtype == torch.float32):
+        raise RuntimeError("gt_points_align: fp32 pred, conf and gt")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("gt_points_align: bool or uint8 mask")
+    if pred.shape[-1] != 3 or gt.shape[-1] != 3:
+        raise RuntimeError("gt_points_align: points with a last dimension of 3")
+    strides = [_batch_block(t, inner, "gt_points_align")
+               for t, inner in ((pred, 3 * P), (conf, P), (gt, 3 * P), (mask, P))]
+    dev = pred.device
+    T = torch.empty(B, 4, 4, device=dev, dtype=torch.float32)
+    scale = torch.empty(B, device=dev, dtype=torch.float32)
+    state = torch.empty(B, GT_POINTS_STATE_WORDS, device=dev, dtype=torch.int64)
+    L = lib()
+    ws = _ws_bytes(dev, int(L.vggt_gt_points_align_ws_bytes(B, P)))  # 0 bytes: the call names the shape's error
+    wp = (ws.data_ptr() + 15) // 16 * 16  # _ws_bytes holds 8 bytes more than asked
+    rc = L.vggt_gt_points_align(_p(pred), strides[0], _p(conf), strides[1], _p(gt), strides[2], _p(mask), strides[3],
+                                B, P, float(q), int(columns), _p(T), _p(scale), _p(state), ctypes.c_void_p(wp),
+                                ws.numel() * 8 - (wp - ws.data_ptr()), _stream())
+    _check(rc, "vggt_gt_points_align")
+    return T, scale, state
+
+
+def gt_points_state(state: torch.Tensor) -> list:
+    """The state records of gt_points_align on the host (this one synchronises): per
+    element n (kept pixels), nan (NaN confidences), and thr, a, c as fp32 tensors'
+    Python floats (a and c: the two order statistics thr is interpolated from)."""
+    s = state.detach().cpu().reshape(-1, GT_POINTS_STATE_WORDS)
+    out = []
+    for row in s:
+        f = row[2:4].view(torch.float32)
+        out.append({"n": int(row[0]), "nan": int(row[1]), "thr": float(f[0]), "a": float(f[1]), "c": float(f[2])})
     return out
 
 

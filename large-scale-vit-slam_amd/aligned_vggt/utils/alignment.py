@@ -19,9 +19,18 @@ Two kinds of callers:
     when the pose encoding and the GT extrinsics are fp32 tensors on one HIP
     device: the scale / transform stays on the device and nothing synchronises.
     Host tensors, other dtypes and VGGT_GT_ALIGN=torch run the reference's host
-    code.  ``sim3_from_points`` stays on the host: its ``reshape(3, -1)`` of an
-    (n, 3) selection is not the transpose a kernel would compute, and it runs
-    once per evaluated sequence.
+    code;
+  * ``sim3_from_points`` (``umeyama_alignment_from_points``) takes the kernel
+    ``vggt_gt_points_align`` (csrc/gt_points.hip) when its four arguments are
+    tensors on one HIP device, fp32 with a bool or uint8 mask: numpy's fp32
+    percentile by radix select, the selection compacted in boolean indexing's
+    order, and Umeyama's closed form in fp64, with transform and scale left on
+    the device.  The reference's ``reshape(3, -1)`` of the (n, 3) selection
+    interleaves coordinates (it is not the transpose); the kernel reads the
+    compacted rows that way too (``columns="reference"``), and
+    ``columns="points"`` is the per-point fit.  Arrays, host tensors, other
+    dtypes, mixed placements and VGGT_GT_ALIGN=torch run the reference's numpy
+    code.
 """
 from __future__ import annotations
 
@@ -442,9 +451,50 @@ def _umeyama_alignment_from_poses_device(predictions: dict, batch: dict, seq_wid
         predictions["depth"] = d
 
 
+def _points_align_kernel_applies(pred_points, pred_confidence, target_points, target_point_mask) -> bool:
+    """All four tensors on one HIP device, fp32 values and a bool or uint8 mask;
+    VGGT_GT_ALIGN=torch (read per call) keeps the host code."""
+    if os.environ.get("VGGT_GT_ALIGN", "") == "torch":
+        return False
+    ts = (pred_points, pred_confidence, target_points, target_point_mask)
+    if not all(torch.is_tensor(t) for t in ts) or not pred_points.is_cuda:
+        return False
+    return (all(t.device == pred_points.device for t in ts)
+            and all(t.dtype == torch.float32 for t in ts[:3])
+            and target_point_mask.dtype in (torch.bool, torch.uint8))
+
+
+_POINT_COLUMNS = ("reference", "points")
+
+
 def umeyama_alignment_from_points(pred_points, pred_confidence, target_points, target_point_mask,
-                                  confidence_threshold: int) -> tuple:
-    """alignment.py:372-426 (percentile-thresholded Umeyama on point maps)."""
+                                  confidence_threshold: int, *, columns: str = "reference") -> tuple:
+    """alignment.py:372-426 (percentile-thresholded Umeyama on point maps).
+
+    ``columns="reference"`` fits the reference's samples, the ``reshape(3, -1)`` of the
+    (n, 3) selection (sic); ``columns="points"`` fits the selected points themselves (the
+    transpose), as the reference's docstring describes.
+
+    Four tensors on one HIP device (fp32, bool or uint8 mask) take the kernel
+    ``vggt_gt_points_align``: the result is ``(T (B, 4, 4), scales (B,))`` as fp32 device
+    tensors with no graph attached (the reference detaches too), and nothing visits the
+    host.  A batch element with no selected pixel gives NaN there; the host route raises
+    inside LAPACK.  Everything else (arrays, host tensors, other dtypes, mixed placements,
+    VGGT_GT_ALIGN=torch) runs the reference's numpy code and returns fp32/fp64 arrays."""
+    if columns not in _POINT_COLUMNS:
+        raise ValueError(f"columns must be one of {_POINT_COLUMNS}, got {columns!r}")
+    if _points_align_kernel_applies(pred_points, pred_confidence, target_points, target_point_mask):
+        from .. import _native
+
+        def blocks(t):  # per-batch blocks contiguous, as [:, :seq_width] of a contiguous tensor is
+            t = t.detach()
+            return t if t[0].is_contiguous() else t.contiguous()
+        with torch.no_grad():
+            T, scales, _state = _native.gt_points_align(
+                blocks(pred_points), blocks(pred_confidence), blocks(target_points), blocks(target_point_mask),
+                float(confidence_threshold), _POINT_COLUMNS.index(columns))
+        return T, scales
+
     def np_(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
     pred_points, target_points = np_(pred_points), np_(target_points)
@@ -453,7 +503,10 @@ def umeyama_alignment_from_points(pred_points, pred_confidence, target_points, t
     for b in range(pred_points.shape[0]):
         thr = np.percentile(pred_confidence[b], confidence_threshold)
         m = (target_point_mask[b] > 0) & (pred_confidence[b] >= thr) & (pred_confidence[b] > 1e-5)
-        r, t, c = umeyama(pred_points[b][m].reshape(3, -1), target_points[b][m].reshape(3, -1))
+        if columns == "reference":
+            r, t, c = umeyama(pred_points[b][m].reshape(3, -1), target_points[b][m].reshape(3, -1))
+        else:
+            r, t, c = umeyama(pred_points[b][m].T, target_points[b][m].T)
         pose = np.pad(r, ((0, 1), (0, 1)), mode="constant")
         pose[:3, 3] = t
         pose[3, 3] = 1.0

@@ -1,6 +1,7 @@
-// What the dense one-pass kernels of points.hip (k-th value), loss.hip (depth loss) and gt_align.hip (GT
-// depth scale) share: the classification of a float on its bits, the order-preserving key of the radix
-// selects, the four-element loads and stores, the 256-bin scan of the pick kernels, the fixed-order
+// What the dense one-pass kernels of points.hip (k-th value), loss.hip (depth loss), gt_align.hip (GT
+// depth scale) and gt_points.hip (GT point alignment) share: the classification of a float on its bits,
+// the order-preserving key of the radix selects and the histogram step of a select pass, the
+// four-element loads and stores, the 256-bin scan of the pick kernels, the fixed-order
 // reduction of a workgroup's partial record, and the grid size.  No function here holds a floating-point
 // multiply followed by an add, so the contraction setting of the including file changes nothing in it;
 // the per-pixel arithmetic (ga_term, dl_term, bl_axis, bl_value) stays in its own file under that
@@ -32,6 +33,25 @@ __device__ __forceinline__ unsigned int f32_key_zeros_equal(float v) {
 __device__ __forceinline__ float f32_unkey(unsigned int k) {
   if (k == 0xffffffffu) return __uint_as_float(F32_QNAN);
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// One element of a radix-select histogram pass (vggt_kth_value_f32, the threshold of vggt_gt_points_align): the
+// digit at `shift` of v's key is counted in the workgroup's 256-bin LDS histogram when the element exists and
+// its higher digits (mask) equal the prefix.  Every lane of the wave calls it together (ballots).
+__device__ __forceinline__ void radix_digit_add(unsigned int* hist, float v, unsigned int prefix, unsigned int mask,
+                                                int shift, bool in_range) {
+  const unsigned int key = f32_key_zeros_equal(v);  // torch.kthvalue's order: -0 == +0
+  const bool take = in_range && (key & mask) == prefix;
+  const unsigned int digit = (key >> shift) & 255u;
+  const unsigned long long takers = __ballot(take);
+  if (takers == 0) return;  // wave-uniform
+  // Confidences share their top digits: when one digit holds the whole wave, one add of the lane count.
+  const unsigned int first = __shfl(digit, __ffsll((long long)takers) - 1, 64);
+  if (__ballot(take && digit == first) == takers) {
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)takers) - 1) atomicAdd(&hist[first], (unsigned int)__popcll(takers));
+  } else if (take) {
+    atomicAdd(&hist[digit], 1u);
+  }
 }
 
 // Four consecutive elements from e of `total`: one 128-bit (mask: 32-bit) access when VEC and all four

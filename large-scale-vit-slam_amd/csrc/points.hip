@@ -57,22 +57,6 @@ struct KthState {
 constexpr size_t KTH_HIST_BYTES = (size_t)KTH_PASSES * KTH_BINS * sizeof(unsigned long long);
 constexpr size_t KTH_WS_BYTES = KTH_HIST_BYTES + sizeof(KthState);
 
-__device__ __forceinline__ void kth_add(unsigned int* hist, float v, unsigned int prefix, unsigned int mask,
-                                        int shift, bool in_range) {
-  const unsigned int key = f32_key_zeros_equal(v);  // torch.kthvalue's order: -0 == +0
-  const bool take = in_range && (key & mask) == prefix;
-  const unsigned int digit = (key >> shift) & (KTH_BINS - 1);
-  const unsigned long long takers = __ballot(take);
-  if (takers == 0) return;  // wave-uniform
-  // Confidences share their top digits: when one digit holds the whole wave, one add of the lane count.
-  const unsigned int first = __shfl(digit, __ffsll((long long)takers) - 1, 64);
-  if (__ballot(take && digit == first) == takers) {
-    if ((int)(threadIdx.x & 63) == __ffsll((long long)takers) - 1) atomicAdd(&hist[first], (unsigned int)__popcll(takers));
-  } else if (take) {
-    atomicAdd(&hist[digit], 1u);
-  }
-}
-
 // One pass: the histogram of digit `pass` (from the top) over the elements that match the state's prefix.
 __global__ __launch_bounds__(KTH_THREADS) void kth_hist_kernel(const float* __restrict__ x, int64_t n, int pass,
                                                                unsigned long long* __restrict__ hist_all,
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(KTH_THREADS) void kth_hist_kernel(const float* __re
 #pragma unroll
     for (int u = 0; u < KTH_UNROLL; ++u) v[u] = i + u * stride < n ? x[i + u * stride] : 0.f;  // loads first
 #pragma unroll
-    for (int u = 0; u < KTH_UNROLL; ++u) kth_add(hist, v[u], prefix, mask, shift, i + u * stride < n);
+    for (int u = 0; u < KTH_UNROLL; ++u) radix_digit_add(hist, v[u], prefix, mask, shift, i + u * stride < n);
   }
   __syncthreads();
   const unsigned int c = hist[tid];

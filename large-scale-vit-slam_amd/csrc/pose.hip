@@ -402,18 +402,6 @@ __global__ __launch_bounds__(64) void pose_align_kernel(
 
 // ---- GT alignment of a merged sequence from its poses (alignment.py:131-242, :325-370, :6-59)
 
-// Umeyama's closed form (alignment.py:6-59) from the centred cross-covariance Sg = E[(y - my)(x - mx)^T]
-// and sigma_x = E|x - mx|^2: R = U diag(1, 1, d) V^T, c = tr(D diag(1, 1, d)) / sigma_x, on the SVD that
-// irls_solve (align.hip) takes too (small_eig.h).
-__device__ void umeyama3(const double Sg[3][3], double sigma_x, double R[3][3], double* c_out) {
-  double U[3][3], Vs[3][3], sv[3], det;
-  svd3_for_umeyama(Sg, U, Vs, sv, &det);
-  const double d = det < 0 ? -1.0 : 1.0;  // the reflection fix (:39-40)
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + d * U[i][2] * Vs[j][2];
-  *c_out = (sv[0] + sv[1] + d * sv[2]) / sigma_x;  // sigma_x == 0: inf or NaN, as the reference's 1 / sigma_x
-}
-
 // One 64-lane workgroup per batch element, lane-stride over frames.  Sums are per-lane fp64
 // partials combined by lane 0 in lane order (no atomics, independent of the grid), every result is
 // rounded to fp32 once.  enc / enc_out are not __restrict__: enc_out may be enc (every read of the

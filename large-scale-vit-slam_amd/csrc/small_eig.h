@@ -1,7 +1,7 @@
 // The small fp64 solvers of the pose and Sim(3) kernels, run by one lane: the 3x3 symmetric
 // eigen-decomposition and the SVD that Umeyama's closed form takes from it (irls_solve in align.hip,
-// umeyama3 in pose.hip), and the top eigenvector of a symmetric 4x4 (the Markley quaternion mean of
-// pose_compose_kernel and pose_align_kernel, pose.hip).
+// umeyama3 below for pose.hip and gt_points.hip), and the top eigenvector of a symmetric 4x4 (the Markley
+// quaternion mean of pose_compose_kernel and pose_align_kernel, pose.hip).
 //
 // Plain C++ apart from the two qualifiers, so that a host program can define them away and run the
 // very same code (tests/small_eig_host.cpp).
@@ -119,6 +119,18 @@ static __device__ void svd3_for_umeyama(const double Sg[3][3], double U[3][3], d
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) UVt[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + U[i][2] * Vs[j][2];
   *det_UVt = det3(UVt);
+}
+
+// Umeyama's closed form (alignment.py:6-59) from the centred cross-covariance Sg = E[(y - my)(x - mx)^T]
+// and sigma_x = E|x - mx|^2: R = U diag(1, 1, d) V^T, c = tr(D diag(1, 1, d)) / sigma_x, on the SVD above
+// (gt_pose_align_kernel in pose.hip, gp_solve_kernel in gt_points.hip; not every includer calls it).
+[[maybe_unused]] static __device__ void umeyama3(const double Sg[3][3], double sigma_x, double R[3][3], double* c_out) {
+  double U[3][3], Vs[3][3], sv[3], det;
+  svd3_for_umeyama(Sg, U, Vs, sv, &det);
+  const double d = det < 0 ? -1.0 : 1.0;  // the reflection fix (:39-40)
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + d * U[i][2] * Vs[j][2];
+  *c_out = (sv[0] + sv[1] + d * sv[2]) / sigma_x;  // sigma_x == 0: inf or NaN, as the reference's 1 / sigma_x
 }
 
 // Largest-eigenvalue unit eigenvector of a symmetric 4x4 (cyclic Jacobi, fp64).  The winning column is
